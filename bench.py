@@ -9,9 +9,11 @@ own 100M-word shard of an N x 100M-word node dictionary (rank 0's is the one abo
 PMK, no collective on the data path): weak scaling.
 
 The JSON line carries the PBKDF2 kernel's roofline (integer VALU bound) from HIP events recorded around each
-launch on the stream it runs on, and the CPU baseline (the OpenSSL restatement of check_key_m22000 from
-oracle/, timed on this host's cores on a bounded sample of the same workload: 1 thread = one PHP request, and
-the box's CPU share).
+launch on the stream it runs on.  A plain run sets up, warms up, times the steps and prints the line.  --full adds
+what takes runs of its own: the untimed checks of the timed steps' hits against the oracle (hits_verified) and the
+CPU baseline (the OpenSSL restatement of check_key_m22000 from oracle/, timed on this host's cores on a bounded
+sample of the same workload: 1 thread = one PHP request, and the box's CPU share).  --dump-outputs DIR writes what
+the timed steps returned to their caller as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -130,8 +132,17 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: every rank builds its shard schedule and runs the control plane only (gloo "
                          "barrier, max/sum reductions); rank 0 prints the ranks' coverage (tests the N-rank path)")
-    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=8, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else the line can carry: the CPU baseline (unless "
+                         "--no-cpu-baseline) and the untimed checks of the results against the oracle (hits_verified; "
+                         "exit code 3 when one fails).  Without it a run sets up, warms up, times the steps and prints "
+                         "the line, with cpu_baseline and hits_verified null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2/c3/c4: after the timed steps write what the timed path returned to its caller -- the "
+                         "candidates each step loaded and the hit records of the timed steps, the last one's "
+                         "included, in a fixed order -- as DIR/<name>.npy (float64 / float32)")
     ap.add_argument("--batch", type=int, default=1 << 24,
                     help="candidates per step per GPU (one PBKDF2 launch of 64 wave rounds; 4M-candidate steps "
                          "measured 0.2 %% slower per PMK: one launch tail per 16 rounds, profiles/r02/batch_size)")
@@ -255,6 +266,30 @@ def verify_timed_hits(w, hits, batches):
         "expected_pairs": len(w.expected), "timed_expected_reports": sum(scans.get(b, 0) for b in w.expected.values())}
 
 
+def dump_outputs(path, prefix, counts, hits, last_batch, batch_of):
+    """--dump-outputs: what the timed steps returned to their caller, as path/<prefix><name>.npy.  The scan API hands
+    back two things: the number of candidates each step loaded (`candidates`, float64, one per timed step) and the
+    hit records (dwpa_scan_hits, fetched once after the last step, so they are those of every timed step): candidate
+    id, hashline, nonce correction (NaN where the line has none), endianness (0 LE, 1 BE, NaN) as float64, the 32 PMK
+    bytes as float32, and `hit_in_last_step` (1.0 where the candidate lies in the batch the last timed step scanned).
+    The device appends hits in no fixed order, so the records are sorted by (line, candidate, nc, endian).  A few
+    hundred bytes per hit: far below any size limit."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    nan = float("nan")
+    rows = sorted(((h["line"], h["cand"], h["nc"], h["endian"], h["pmk"]) for h in hits),
+                  key=lambda r: (r[0], r[1], r[2] is not None, r[2] or 0, r[3] or "", r[4]))
+    arrays = {"candidates": np.asarray(counts, dtype=np.float64),
+              "hit_line": np.asarray([r[0] for r in rows], dtype=np.float64),
+              "hit_cand": np.asarray([r[1] for r in rows], dtype=np.float64),
+              "hit_nc": np.asarray([nan if r[2] is None else r[2] for r in rows], dtype=np.float64),
+              "hit_endian": np.asarray([{None: nan, "LE": 0.0, "BE": 1.0}[r[3]] for r in rows], dtype=np.float64),
+              "hit_pmk": np.frombuffer(b"".join(r[4] for r in rows), dtype=np.uint8).astype(np.float32).reshape(-1, 32),
+              "hit_in_last_step": np.asarray([float(batch_of(r[1]) == last_batch) for r in rows], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+
+
 class Workload:
     """One BASELINE.json config as a sequence of steps over HBM-resident candidates."""
     name = ""
@@ -307,6 +342,7 @@ def build_c2(args, local, S, Scan, Dictionary, shard=0):
     pmk_of = _pmk_cache(S, w.essid)
     w.load, w.check, w.plant_batch = load, check, w.plant // w.B
     w.genuine, w.expected = genuine, {(0, w.plant): w.plant_batch}
+    w.batch_of = lambda cand: cand // w.B
     w.cpu_line, w.cpu_keys, w.cpu_what = w.line, cpu_keys, "dictionary words"
     w.algo_bytes_per_pmk = ALGO_BYTES_PER_PMK
     return w
@@ -344,6 +380,7 @@ def build_c4(args, local, S, Scan, Dictionary, shard=0):
     pmk_of = _pmk_cache(S, w.essid)
     w.load, w.check, w.plant_batch = load, check, w.plant // w.B
     w.genuine, w.expected = genuine, {(0, w.plant): w.plant_batch}
+    w.batch_of = lambda cand: cand // w.B
     w.cpu_line, w.cpu_keys = w.line, lambda m: [b"%08d" % v for v in range(w.plant - m + 1, w.plant + 1)]
     w.cpu_what = "8-digit candidates"
     w.algo_bytes_per_pmk = ALGO_BYTES_PER_PMK
@@ -445,6 +482,7 @@ def build_c3(args, local, S, Scan, Dictionary, shard=0):
     w.cpu_what = "rule candidates (word-major, 8..63) of one ESSID's line"
     w.algo_bytes_per_pmk = 32 + 40 * len(lines) / w.groups
     w.plant_batch = (w.plants[0][1] // w.nrules) // w.words_per_step if w.plants else 0
+    w.batch_of = lambda cand: (cand // w.nrules) // w.words_per_step
     return w
 
 
@@ -553,7 +591,10 @@ def main():
         from tools.cmin import from_costs
         C_MIN_CYCLES = from_costs(args.peak_costs)["c_min_model"]
         PEAK_COMPRESSIONS = SIMDS * CLOCK_HZ * 64 / C_MIN_CYCLES
-    import torch.distributed as dist
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and (args.workload not in ("c2", "c3", "c4") or args.scaling == "strong" or args.dry_run):
+        sys.exit("bench.py: --dump-outputs is defined for the weak-scaling scan workloads (c2, c3, c4)")
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -576,7 +617,8 @@ def main():
         return main_strong(args, world, rank, local)
     if world > 1:
         # control plane only (barrier, max-over-ranks time, sum of PMKs): the data path shards the keyspace and
-        # never exchanges data, so there is no RCCL collective on the GPU.
+        # never exchanges data, so there is no RCCL collective on the GPU.  One rank alone never imports torch.
+        import torch.distributed as dist
         dist.init_process_group("gloo")
 
     import dwpa_amd
@@ -647,21 +689,26 @@ def main():
     else:
         total = float(done)
 
-    # correctness (untimed): the hits of the timed steps, each re-derived, and every timed scan of the planted batch
-    # reporting the plant; then one more scan of the planted batch, which must report it too
+    timed_batches = [b for _, b in weak_units(rank, args.warmup, args.steps, w.nbatches, rot)]
     timed_hits = []
-    for k in range(P):
-        timed_hits += w.scans[k].hits(streams[k].handle)
-    timed_ok, hits_check = verify_timed_hits(w, timed_hits,
-                                             [b for _, b in weak_units(rank, args.warmup, args.steps, w.nbatches,
-                                                                       rot)])
-    step(w.plant_batch, 0)
-    plant_ok = bool(w.check(w.scans[0].hits(streams[0].handle)))
-    hits_check["plant_rescan_ok"] = plant_ok
-    verified = timed_ok and plant_ok
-    if world > 1:  # every rank's own planted PSK must come back (each rank scans its own shard)
-        from dwpa_amd.shard import all_ranks
-        verified = all_ranks(dist, verified)
+    if args.full or args.dump_outputs:
+        for k in range(P):
+            timed_hits += w.scans[k].hits(streams[k].handle)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "" if world == 1 else f"rank{rank}_", counts, timed_hits, timed_batches[-1],
+                     w.batch_of)
+    # correctness (untimed, --full): the hits of the timed steps, each re-derived, and every timed scan of the planted
+    # batch reporting the plant; then one more scan of the planted batch, which must report it too
+    verified = hits_check = None
+    if args.full:
+        timed_ok, hits_check = verify_timed_hits(w, timed_hits, timed_batches)
+        step(w.plant_batch, 0)
+        plant_ok = bool(w.check(w.scans[0].hits(streams[0].handle)))
+        hits_check["plant_rescan_ok"] = plant_ok
+        verified = timed_ok and plant_ok
+        if world > 1:  # every rank's own planted PSK must come back (each rank scans its own shard)
+            from dwpa_amd.shard import all_ranks
+            verified = all_ranks(dist, verified)
 
     per_launch = list(counts) if w.groups > 1 else [c / w.groups for c in counts]
     pmk_per_launch = sum(per_launch) / len(per_launch)
@@ -670,7 +717,7 @@ def main():
     if rank == 0:
         value = total / elapsed
         cpu = None
-        if not args.no_cpu_baseline and world == 1 and w.cpu_keys:
+        if args.full and not args.no_cpu_baseline and world == 1 and w.cpu_keys:
             cpu = cpu_baseline(w.cpu_line, w.cpu_keys, args.cpu_seconds, w.cpu_what)
         result = {
             "metric": METRIC,
@@ -698,6 +745,7 @@ def main():
                              else "k_pbkdf2_gfx950 (gfx950 VALU issue pass)",
             "rank0_local_s": round(elapsed_local, 4),
             "pipeline": P,
+            "full": args.full,
         }
         emit(result)
     for sc in w.scans:
@@ -705,7 +753,7 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and not verified:
+    if rank == 0 and verified is False:
         sys.exit(3)
 
 
@@ -833,17 +881,19 @@ def main_strong(args, world, rank, local):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     done = float(sum(c for _, c in sched) * args.steps)
-    hits = sc.hits(hs)
-    want = args.steps if lo <= w.plant < hi else 0
-    good = sum(1 for h in hits if h["cand"] == w.plant and h["pmk"] == S.pmk(b"%08d" % w.plant, w.essid))
-    ok_local = good == want and len(hits) == want
+    ok_local = None
+    if args.full:  # untimed check: the plant with its PMK once per timed pass on the rank holding it, nothing else
+        hits = sc.hits(hs)
+        want = args.steps if lo <= w.plant < hi else 0
+        good = sum(1 for h in hits if h["cand"] == w.plant and h["pmk"] == S.pmk(b"%08d" % w.plant, w.essid))
+        ok_local = good == want and len(hits) == want
     kms = [a.elapsed_ms(b) for step in kev for a, b in step]
     kernel_ms = sum(kms) / len(kms)
     kernel_pmk_s = sum(c for _, c in sched) * args.steps / (sum(kms) * 1e-3)
     if world > 1:
         from dwpa_amd.shard import all_ranks
         elapsed, total = reduce_timing(dist, elapsed, done)
-        verified = all_ranks(dist, ok_local)
+        verified = all_ranks(dist, ok_local) if args.full else None
         shards = [None] * world
         dist.all_gather_object(shards, [lo, hi, len(sched), round(elapsed_local, 4)])
     else:
@@ -851,7 +901,7 @@ def main_strong(args, world, rank, local):
     if rank == 0:
         t_exhaust = elapsed / args.steps
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline(w.cpu_line, w.cpu_keys, args.cpu_seconds, w.cpu_what)
         pmk_per_launch = sum(c for _, c in sched) / len(sched)
         traffic_pmk = TRAFFIC_BYTES_PER_PMK["c4"]
@@ -869,14 +919,14 @@ def main_strong(args, world, rank, local):
             "shards": shards,
             "roofline": roofline_block("k_pbkdf2_gfx950_q (rank 0)", kernel_pmk_s, pmk_per_launch, kernel_ms,
                                        traffic_pmk, TRAFFIC_SOURCE["c4"], ALGO_BYTES_PER_PMK, args.peak_costs),
-            "cpu_baseline": cpu, "hits_verified": verified,
+            "cpu_baseline": cpu, "hits_verified": verified, "full": args.full,
             "hits_checked": "the planted PSK 73019412 with its PMK, once per timed pass, on the rank holding it; "
                             "no other hit on any rank"})
     sc.close()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and not verified:
+    if rank == 0 and verified is False:
         sys.exit(3)
 
 
@@ -951,7 +1001,9 @@ def main_ffi(args, world, rank, local):
     got = batch.results()
     same = all(b.results() == got for b in batches[1:])
     mismatches = None
-    if args.workload == "c1":
+    if not args.full:
+        verified = None
+    elif args.workload == "c1":
         verified = bool(got[0]) and got[0][0] == psk and got[0][3] == S.pmk(psk, bytes.fromhex(line.split(b"*")[5].decode()))
     else:
         # every job exactly: the planted key's [PSK, NC, endian, PMK] tuple re-derived by the oracle from that key
@@ -967,13 +1019,14 @@ def main_ffi(args, world, rank, local):
             exp = list(ex.map(expected, range(len(jobs))))
         mismatches = sum(1 for g, e in zip(got, exp) if g != e)
         verified = mismatches == 0 and sum(1 for e in exp if e) >= 0.85 * len(jobs)
-    verified = verified and same
-    if world > 1:  # every replica's results must check
-        from dwpa_amd.shard import all_ranks
-        verified = all_ranks(dist, verified)
+    if args.full:
+        verified = verified and same
+        if world > 1:  # every replica's results must check
+            from dwpa_amd.shard import all_ranks
+            verified = all_ranks(dist, verified)
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline_jobs(jobs, args.cpu_seconds)
         emit({
             "metric": METRIC, "value": round(total / elapsed, 1), "unit": "PMK/s", "n_gpus": world,
@@ -981,7 +1034,7 @@ def main_ffi(args, world, rank, local):
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
             "config": {"workload": desc, "jobs": len(jobs), "keys_per_step": batch.nkeys * callers,
                        "callers": callers, "parallelism": f"replicas x{world}"},
-            "roofline": None, "cpu_baseline": cpu, "hits_verified": verified,
+            "roofline": None, "cpu_baseline": cpu, "hits_verified": verified, "full": args.full,
             "hits": sum(1 for g in got if g),
             "mismatches": mismatches if args.workload == "c5" else None,
             "window_unix": window,
@@ -991,7 +1044,7 @@ def main_ffi(args, world, rank, local):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and not verified:
+    if rank == 0 and verified is False:
         sys.exit(3)
 
 

@@ -165,6 +165,31 @@ def test_timed_hits_verification():
     assert ok and d["timed_plant_scans"] == 0
 
 
+def test_dump_outputs_sorted_float_arrays(tmp_path):
+    """bench.py --dump-outputs: the step counts and the hit records as float .npy files, the records in the same
+    order whatever order the device reported them in, PMKID hits (no nonce correction) as NaN."""
+    import numpy as np
+
+    import bench
+
+    eapol = {"line": 1, "cand": 40, "nc": -3, "endian": "BE", "pmk": bytes(range(32))}
+    pmkid = {"line": 0, "cand": 7, "nc": None, "endian": None, "pmk": bytes(32)}
+    for name, hits in (("a", [eapol, pmkid, eapol]), ("b", [pmkid, eapol, eapol])):
+        bench.dump_outputs(str(tmp_path / name), "", [64, 32], hits, 2, lambda cand: cand // 16)
+    a = {f.name: np.load(f) for f in sorted((tmp_path / "a").iterdir())}
+    b = {f.name: np.load(f) for f in sorted((tmp_path / "b").iterdir())}
+    assert set(a) == set(b) == {n + ".npy" for n in ("candidates", "hit_line", "hit_cand", "hit_nc", "hit_endian",
+                                                   "hit_pmk", "hit_in_last_step")}
+    assert all(np.array_equal(a[n], b[n], equal_nan=True) for n in a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["candidates.npy"].tolist() == [64.0, 32.0]
+    assert a["hit_line.npy"].tolist() == [0.0, 1.0, 1.0] and a["hit_cand.npy"].tolist() == [7.0, 40.0, 40.0]
+    assert np.isnan(a["hit_nc.npy"][0]) and a["hit_nc.npy"][1:].tolist() == [-3.0, -3.0]
+    assert np.isnan(a["hit_endian.npy"][0]) and a["hit_endian.npy"][1:].tolist() == [1.0, 1.0]
+    assert a["hit_pmk.npy"].shape == (3, 32) and a["hit_pmk.npy"][1].tolist() == list(range(32))
+    assert a["hit_in_last_step.npy"].tolist() == [0.0, 1.0, 1.0]
+
+
 def test_node_mode_dry_run_one_process():
     """`bench.py --workload c2files --gpus 8` is the client's node mode: one process over a mask
     of 8 devices, no rank processes.  Its --dry-run drives the library's reader and item queue (ChunkSource +

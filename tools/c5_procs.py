@@ -24,7 +24,8 @@ def main():
     for k in [int(x) for x in args.procs.split(",")]:
         start = time.time() + 40.0  # every process has built its batch and warmed up before the window opens
         ps = [subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--steps",
-                                str(args.steps), "--warmup", "3", "--no-cpu-baseline", "--start-at", repr(start)],
+                                str(args.steps), "--warmup", "3", "--full", "--no-cpu-baseline", "--start-at",
+                                repr(start)],
                                stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env) for _ in range(k)]
         outs = []
         for p in ps:
