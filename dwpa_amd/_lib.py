@@ -153,7 +153,15 @@ SIGNATURES = {
     "dwpa_event_record": ([_P, _P], ctypes.c_int),
     "dwpa_event_elapsed_ms": ([_P, _P, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
     "dwpa_event_destroy": ([_P], ctypes.c_int),
+    "dwpa_debug_pbkdf2_kernels": ([ctypes.c_int], ctypes.c_uint32),  # test hook, not in include/dwpa22000.h
 }
+
+# Bit i of dwpa_debug_pbkdf2_kernels' mask (csrc/kernels.hpp Pbkdf2Kernel): the hipcc-scheduled kernels of kernels.hip,
+# then the issue-pass code object's (one ESSID / per-slot salt / ESSID groups; _p priority, _q work queue).
+PBKDF2_KERNEL_NAMES = ("k_pbkdf2", "k_pbkdf2_ms", "k_pbkdf2_mg", "k_pbkdf2_ms_tail",
+                       "k_pbkdf2_gfx950", "k_pbkdf2_gfx950_ms", "k_pbkdf2_gfx950_mg",
+                       "k_pbkdf2_gfx950_p", "k_pbkdf2_gfx950_ms_p", "k_pbkdf2_gfx950_mg_p",
+                       "k_pbkdf2_gfx950_q", "k_pbkdf2_gfx950_mg_q")
 
 _lib = None
 
@@ -171,6 +179,14 @@ def load():
             fn.restype = res
         _lib = lib
     return _lib
+
+
+def pbkdf2_kernels(reset: bool = False) -> frozenset:
+    """Names of the PBKDF2 kernels this process has launched since the last reset (the library's test hook): which
+    of pbkdf2_module.cpp's variants a call really ran."""
+    mask = int(load().dwpa_debug_pbkdf2_kernels(1 if reset else 0))
+    assert mask >> len(PBKDF2_KERNEL_NAMES) == 0, hex(mask)
+    return frozenset(n for i, n in enumerate(PBKDF2_KERNEL_NAMES) if mask >> i & 1)
 
 
 def check(rc: int, what: str = "") -> int:

@@ -1698,7 +1698,11 @@ int scan_hits_raw(dwpa_scan* sc, std::vector<HitDev>& out, void* stream) {
     uint32_t nh = 0;
     HIPCHK(hipMemcpyAsync(&nh, (uint32_t*)sc->batch.counters.p + 1, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (nh > sc->batch.hitcap) return DWPA_E_OVERFLOW;
+    if (nh > sc->batch.hitcap) {  // the hits past hitcap were dropped: report it, and leave the scan usable
+        HIPCHK(hipMemsetAsync((uint32_t*)sc->batch.counters.p + 1, 0, 4, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return DWPA_E_OVERFLOW;
+    }
     out.resize(nh);
     if (nh) HIPCHK(hipMemcpyAsync(out.data(), sc->batch.hits.p, nh * sizeof(HitDev), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemsetAsync((uint32_t*)sc->batch.counters.p + 1, 0, 4, s));
@@ -1756,6 +1760,13 @@ using namespace dwpa;
 extern "C" {
 
 int dwpa_abi_version(void) { return DWPA_ABI_VERSION; }
+
+// Test hook, not declared in include/dwpa22000.h: the mask of PBKDF2 entry kernels launched by this process so far
+// (kernels.hpp Pbkdf2Kernel), cleared when `reset` is non-zero.
+uint32_t dwpa_debug_pbkdf2_kernels(int reset) {
+    return reset ? g_pbkdf2_kernels.exchange(0u, std::memory_order_relaxed)
+                 : g_pbkdf2_kernels.load(std::memory_order_relaxed);
+}
 
 int dwpa_init(const dwpa_config* cfg) {
     return guarded([&]() -> int {

@@ -633,6 +633,7 @@ hipError_t launch_pbkdf2_plain(const uint32_t* mid, uint32_t cap, uint32_t base,
                                const uint32_t* counter, const uint32_t* salt, uint32_t nsalt, uint32_t* pmk,
                                hipStream_t s) {
     if (count == 0) return hipSuccess;
+    note_pbkdf2_kernel(PK_PLAIN);
     hipLaunchKernelGGL(k_pbkdf2, dim3(cdiv(count, 256), 2), dim3(256), 0, s, mid, cap, base, count, counter, salt, nsalt,
                        pmk);
     return hipGetLastError();
@@ -650,6 +651,7 @@ hipError_t launch_pbkdf2_ms_plain(const uint32_t* mid, uint32_t cap, uint32_t co
     count = min(count, cap);
     if (count == 0) return hipSuccess;
     const uint32_t launch = (count + LONE_PAD - 1) / LONE_PAD * LONE_PAD;
+    note_pbkdf2_kernel(PK_PLAIN_MS);
     hipLaunchKernelGGL(k_pbkdf2_ms, dim3(cdiv(launch, 256), 2), dim3(256), 0, s, mid, cap, launch, pool, sref, pmk,
                        count);
     return hipGetLastError();
@@ -674,6 +676,7 @@ hipError_t launch_pbkdf2_ms_tail(const uint32_t* mid, uint32_t cap, uint32_t cou
                                  const uint32_t* sref, uint32_t* pmk, uint32_t* flag, uint32_t prio,
                                  uint32_t* raised, hipStream_t s) {
     if (count == 0) return hipSuccess;
+    note_pbkdf2_kernel(PK_PLAIN_MS_TAIL);
     hipLaunchKernelGGL(k_pbkdf2_ms_tail, dim3(cdiv(count, 256), 2), dim3(256), 0, s, mid, cap, count, pool, sref, pmk,
                        flag, prio, raised);
     return hipGetLastError();
@@ -740,6 +743,7 @@ hipError_t launch_pbkdf2_mg_plain(const uint32_t* mid, uint32_t cap, const uint3
                                   const uint32_t* salt, const uint32_t* gsalt, uint32_t* pmk, uint32_t pstride,
                                   hipStream_t s) {
     if (ngroups == 0 || cap == 0) return hipSuccess;
+    note_pbkdf2_kernel(PK_PLAIN_MG);
     hipLaunchKernelGGL(k_pbkdf2_mg, dim3(cdiv((uint64_t)ngroups * cap, 256), 2), dim3(256), 0, s, mid, cap, counter,
                        ngroups, salt, gsalt, pmk, pstride);
     return hipGetLastError();

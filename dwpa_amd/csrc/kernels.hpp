@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "tables.hpp"
 
 namespace dwpa {
@@ -23,6 +25,26 @@ hipError_t launch_pbkdf2_plain(const uint32_t* mid, uint32_t cap, uint32_t base,
                                const uint32_t* counter, const uint32_t* salt, uint32_t nsalt, uint32_t* pmk,
                                hipStream_t s);
 const char* pbkdf2_variant();
+// Which PBKDF2 entry kernels this process has launched: one bit each, set by the launchers (a relaxed fetch_or per
+// launch), read and optionally cleared through dwpa_debug_pbkdf2_kernels (engine.cpp; not part of the public ABI).
+// A mask and not "the last kernel": crack_files launches from one worker thread per device.  The bit order is
+// PBKDF2_KERNEL_NAMES in dwpa_amd/_lib.py.
+enum Pbkdf2Kernel : uint32_t {
+    PK_PLAIN = 1u << 0,          // k_pbkdf2
+    PK_PLAIN_MS = 1u << 1,       // k_pbkdf2_ms
+    PK_PLAIN_MG = 1u << 2,       // k_pbkdf2_mg
+    PK_PLAIN_MS_TAIL = 1u << 3,  // k_pbkdf2_ms_tail
+    PK_ONE = 1u << 4,            // k_pbkdf2_gfx950
+    PK_MS = 1u << 5,             // k_pbkdf2_gfx950_ms
+    PK_MG = 1u << 6,             // k_pbkdf2_gfx950_mg
+    PK_ONE_P = 1u << 7,          // k_pbkdf2_gfx950_p
+    PK_MS_P = 1u << 8,           // k_pbkdf2_gfx950_ms_p
+    PK_MG_P = 1u << 9,           // k_pbkdf2_gfx950_mg_p
+    PK_ONE_Q = 1u << 10,         // k_pbkdf2_gfx950_q
+    PK_MG_Q = 1u << 11,          // k_pbkdf2_gfx950_mg_q
+};
+extern std::atomic<uint32_t> g_pbkdf2_kernels;
+inline void note_pbkdf2_kernel(uint32_t bit) { g_pbkdf2_kernels.fetch_or(bit, std::memory_order_relaxed); }
 // PMKs that give every SIMD of the current device one PBKDF2 wave (two output-block lanes per PMK); 0 on error
 uint32_t pbkdf2_wave_unit();
 // many ESSIDs per launch: slot s uses the salt entry pool + sref[s] = {nsalt, [2][nsalt][16] words}

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <mutex>
 
@@ -26,6 +27,7 @@ struct Fns {
 };
 static std::mutex g_mod_mu;
 static std::map<int, Fns> g_fn;
+std::atomic<uint32_t> g_pbkdf2_kernels{0};
 
 static bool env_flag(const char* name) {
     const char* e = getenv(name);
@@ -99,12 +101,15 @@ hipError_t launch_pbkdf2(const uint32_t* mid, uint32_t cap, uint32_t base, uint3
         void* qargs[] = {(void*)&mid, (void*)&cap, (void*)&base, (void*)&count, (void*)&counter,
                          (void*)&salt, (void*)&nsalt, (void*)&pmk, (void*)&work};
         const uint32_t blocks = (uint32_t)(8 * fn.level_lanes / 256);
+        note_pbkdf2_kernel(PK_ONE_Q);
         return hipModuleLaunchKernel(fn.one_q, blocks, 1, 1, 256, 1, 1, 0, s, qargs, nullptr);
     }
     void* args[] = {(void*)&mid, (void*)&cap, (void*)&base, (void*)&count, (void*)&counter,
                     (void*)&salt, (void*)&nsalt, (void*)&pmk};
     const uint32_t wg = WG;
-    return hipModuleLaunchKernel(use_prio(fn, std::min<uint64_t>(count, cap > base ? cap - base : 0)) ? fn.one_p : fn.one,
+    const bool prio = use_prio(fn, pmks);
+    note_pbkdf2_kernel(prio ? PK_ONE_P : PK_ONE);
+    return hipModuleLaunchKernel(prio ? fn.one_p : fn.one,
                                  (count + wg - 1) / wg, 2, 1, wg, 1, 1, 0, s, args,
                                  nullptr);
 }
@@ -119,7 +124,9 @@ hipError_t launch_pbkdf2_ms(const uint32_t* mid, uint32_t cap, uint32_t count, c
     if (lone_waves(fn, std::min(count, cap))) return launch_pbkdf2_ms_plain(mid, cap, count, pool, sref, pmk, s);
     void* args[] = {(void*)&mid, (void*)&cap, (void*)&count, (void*)&pool, (void*)&sref, (void*)&pmk};
     const uint32_t wg = WG;
-    return hipModuleLaunchKernel(use_prio(fn, std::min(count, cap)) ? fn.ms_p : fn.ms, (count + wg - 1) / wg, 2, 1, wg, 1, 1, 0, s, args,
+    const bool prio = use_prio(fn, std::min(count, cap));
+    note_pbkdf2_kernel(prio ? PK_MS_P : PK_MS);
+    return hipModuleLaunchKernel(prio ? fn.ms_p : fn.ms, (count + wg - 1) / wg, 2, 1, wg, 1, 1, 0, s, args,
                                  nullptr);
 }
 
@@ -141,12 +148,15 @@ hipError_t launch_pbkdf2_mg(const uint32_t* mid, uint32_t cap, const uint32_t* c
         void* qargs[] = {(void*)&mid, (void*)&cap, (void*)&counter, (void*)&ngroups, (void*)&salt, (void*)&gsalt,
                          (void*)&pmk, (void*)&pstride, (void*)&work};
         const uint32_t blocks = (uint32_t)(8 * fn.level_lanes / 256);
+        note_pbkdf2_kernel(PK_MG_Q);
         return hipModuleLaunchKernel(fn.mg_q, blocks, 1, 1, 256, 1, 1, 0, s, qargs, nullptr);
     }
     void* args[] = {(void*)&mid, (void*)&cap, (void*)&counter, (void*)&ngroups, (void*)&salt, (void*)&gsalt,
                     (void*)&pmk, (void*)&pstride};
     const uint32_t wg = WG;
-    return hipModuleLaunchKernel(use_prio(fn, lanes) ? fn.mg_p : fn.mg, (uint32_t)((lanes + wg - 1) / wg), 2, 1, wg, 1, 1, 0, s,
+    const bool prio = use_prio(fn, lanes);
+    note_pbkdf2_kernel(prio ? PK_MG_P : PK_MG);
+    return hipModuleLaunchKernel(prio ? fn.mg_p : fn.mg, (uint32_t)((lanes + wg - 1) / wg), 2, 1, wg, 1, 1, 0, s,
                                  args, nullptr);
 }
 

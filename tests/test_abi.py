@@ -40,6 +40,22 @@ def test_abi_version_and_strerror():
         assert lib.dwpa_strerror(code)
 
 
+def test_debug_pbkdf2_kernels_hook():
+    """dwpa_debug_pbkdf2_kernels (the test hook tests/test_gpu_recall.py reads which PBKDF2 kernel ran from): exported,
+    outside the public header and the ABI version, and an empty mask in a process that has launched nothing."""
+    import subprocess
+    import sys
+    assert hasattr(L.load(), "dwpa_debug_pbkdf2_kernels")
+    assert "dwpa_debug_pbkdf2_kernels" not in declared_symbols()
+    assert len(L.PBKDF2_KERNEL_NAMES) == len(set(L.PBKDF2_KERNEL_NAMES)) == 12
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    child = ("import sys; sys.path.insert(0, sys.argv[1]); from dwpa_amd import _lib as L; lib = L.load(); "
+             "print(lib.dwpa_debug_pbkdf2_kernels(0), lib.dwpa_debug_pbkdf2_kernels(1), sorted(L.pbkdf2_kernels()))")
+    r = subprocess.run([sys.executable, "-c", child, root], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.strip() == "0 0 []"
+
+
 def test_hc_unhex_matches_oracle():
     import dwpa_amd
     for k in [b"$HEX[414243]", b"$HEX[]", b"$HEX[41424]", b"$HEX[41zz]", b"$HEX[4142]x", b"plain", b"$HEX[00ff]",
