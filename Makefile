@@ -7,7 +7,8 @@ OBJ := build/obj
 LIB := dwpa_amd/lib/libdwpa22000.so
 HDRS := $(wildcard $(SRC)/*.hpp) include/dwpa22000.h
 OBJS := $(OBJ)/kernels.o $(OBJ)/rules_dev.o $(OBJ)/engine.o $(OBJ)/m22000_host.o $(OBJ)/crack.o $(OBJ)/rules.o \
-        $(OBJ)/pbkdf2_module.o $(OBJ)/pbkdf2_hsaco.o $(OBJ)/host_crypto.o $(OBJ)/host_check.o
+        $(OBJ)/pbkdf2_module.o $(OBJ)/pbkdf2_hsaco.o $(OBJ)/host_crypto.o $(OBJ)/host_check.o \
+        $(OBJ)/mask.o $(OBJ)/mask_dev.o $(OBJ)/crack_mask.o
 LLVM := /opt/rocm/lib/llvm/bin
 ISSUE_RULE ?= sched=1:alt:orig:asmnop,before_half
 
@@ -55,9 +56,10 @@ $(LIB): $(OBJS)
 oracle:
 	$(MAKE) -s -C oracle
 
-asm: $(SRC)/kernels.hip $(HDRS)
+asm: $(SRC)/kernels.hip $(SRC)/mask_dev.hip $(HDRS)
 	@mkdir -p build/asm
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $< -o build/asm/kernels.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/mask_dev.hip -o build/asm/mask_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 
 clean:
 	rm -rf build $(LIB)
@@ -67,7 +69,8 @@ clean:
 
 tools: tools/bin/valu_peak tools/bin/pbkdf2_lab tools/bin/valu_lat tools/bin/valu_peak64 tools/bin/inflate_bench \
        tools/bin/inflate_check tools/bin/item_queue_check tools/bin/rules_fuzz_asan tools/bin/clock_idle \
-       tools/bin/inflate_check_tsan tools/bin/tail_placement tools/bin/parse_fuzz_asan tools/bin/host_check_fuzz_asan tools/bin/host_pbkdf2_paths tools/bin/vgpr_bank
+       tools/bin/inflate_check_tsan tools/bin/tail_placement tools/bin/parse_fuzz_asan tools/bin/host_check_fuzz_asan tools/bin/host_pbkdf2_paths tools/bin/vgpr_bank \
+       tools/bin/mask_fuzz_asan
 
 tools/bin/valu_lat: tools/valu_lat.hip
 	@mkdir -p tools/bin
@@ -106,6 +109,12 @@ tools/bin/rules_fuzz_asan: tools/rules_fuzz.cpp $(SRC)/rules.cpp $(SRC)/rules.hp
 	@mkdir -p tools/bin
 	$(HIPCC) -O1 -g -std=c++17 -Iinclude -I$(SRC) -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
 	    -o $@ tools/rules_fuzz.cpp $(SRC)/rules.cpp
+
+# host fuzz of the mask language (parser, keyspace, candidates) under AddressSanitizer + UBSan: mask.cpp alone
+tools/bin/mask_fuzz_asan: tools/mask_fuzz.cpp $(SRC)/mask.cpp $(SRC)/mask.hpp include/dwpa22000.h
+	@mkdir -p tools/bin
+	$(HIPCC) -O1 -g -std=c++17 -Iinclude -I$(SRC) -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	    -o $@ tools/mask_fuzz.cpp $(SRC)/mask.cpp
 
 tools/bin/parse_fuzz_asan: tools/parse_fuzz.cpp $(SRC)/m22000_host.cpp $(SRC)/m22000_host.hpp $(SRC)/tables.hpp
 	@mkdir -p tools/bin

@@ -7,13 +7,15 @@ this package is its Python host side:
 * :func:`check_batch`      -- bulk form (put_work / rkg loops)
 * :func:`pbkdf2_pmk`       -- PMK derivation
 * :class:`Scan`            -- device-resident scan of HBM dictionaries / keyspaces (client hot loop, bench)
+* :func:`crack_mask`       -- hashcat ``-a 3`` mask attack (``python -m dwpa_amd.mask`` is its command line);
+  :func:`mask_keyspace` / :func:`mask_candidate` are its host-only helpers
 * :mod:`dwpa_amd.help_crack` -- ``run_cracker`` replacement for help_crack.py
 """
 from ._lib import DwpaError, load  # noqa: F401
-from .m22000 import (BatchJobs, check_batch, check_key_m22000, crack_files, device_count, group_by_essid,  # noqa: F401
-                     check_stats, hash_m22000, hc_unhex, init, parse_m22000, pbkdf2_pmk, rules_count, rules_count_ex,
-                     rules_expand, Scan)
+from .m22000 import (BatchJobs, check_batch, check_key_m22000, crack_files, crack_mask, device_count,  # noqa: F401
+                     group_by_essid, mask_candidate, mask_keyspace, check_stats, hash_m22000, hc_unhex, init,
+                     parse_m22000, pbkdf2_pmk, rules_count, rules_count_ex, rules_expand, Scan)
 
 __all__ = ["DwpaError", "load", "BatchJobs", "check_key_m22000", "check_batch", "pbkdf2_pmk", "hc_unhex", "hash_m22000",
            "crack_files", "rules_count", "rules_count_ex", "check_stats", "rules_expand", "device_count", "Scan",
-           "parse_m22000", "group_by_essid", "init"]
+           "parse_m22000", "group_by_essid", "init", "crack_mask", "mask_keyspace", "mask_candidate"]

@@ -136,6 +136,16 @@ SIGNATURES = {
     "dwpa_scan_set_rules": ([_P, ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int),
     "dwpa_scan_load_rules": ([_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, _P], ctypes.c_int),
     "dwpa_scan_load_numeric": ([_P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _P], ctypes.c_int),
+    "dwpa_mask_keyspace": ([ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(Bytes), ctypes.POINTER(ctypes.c_uint32),
+                            ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_mask_candidate": ([ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(Bytes), ctypes.c_uint64, _P,
+                             ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+    "dwpa_scan_set_mask": ([_P, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(Bytes),
+                            ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_scan_load_mask": ([_P, ctypes.c_uint64, ctypes.c_uint32, _P], ctypes.c_int),
+    "dwpa_crack_mask": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Bytes), ctypes.c_uint64, ctypes.c_uint64,
+                         ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)],
+                        ctypes.c_int),
     "dwpa_scan_pbkdf2": ([_P, ctypes.c_int, _P], ctypes.c_int),
     "dwpa_scan_verify": ([_P, ctypes.c_int, _P], ctypes.c_int),
     "dwpa_scan_run": ([_P, _P], ctypes.c_int),

@@ -43,7 +43,7 @@ struct CrackShared {
     std::atomic<int> error{0};
 };
 
-static std::string outfile_record(const ParsedLine& p, const std::string& psk) {
+std::string outfile_record(const ParsedLine& p, const std::string& psk) {
     const std::string& target = p.kind == LINE_PMKID ? p.pmkid : p.keymic;
     return hex_lower(target.substr(0, 16)) + ":" + hex_lower(p.mac_ap) + ":" + hex_lower(p.mac_sta) + ":" +
            hashcat_plain(p.essid) + ":" + hashcat_plain(psk) + "\n";
@@ -174,7 +174,7 @@ static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, siz
 // DWPA_CRACK_SHARDS_PER_DEVICE=k runs k shard workers per selected device (default 1).  On a one-GPU box k = 2
 // rehearses the multi-device path -- per-worker queues, shard scans and cross-worker line retirement -- that a
 // volunteer's 8-GPU node runs (hashcat uses every device, help_crack.py:773).
-static size_t shards_per_device() {
+size_t crack_shards_per_device() {
     const char* e = getenv("DWPA_CRACK_SHARDS_PER_DEVICE");
     const long k = e ? strtol(e, nullptr, 10) : 1;
     return (size_t)std::min<long>(8, std::max<long>(1, k));
@@ -184,6 +184,31 @@ static size_t shards_per_device() {
 static thread_local dwpa_crack_stats g_last_stats;
 static thread_local std::vector<dwpa_crack_worker> g_last_workers;
 static thread_local bool g_have_stats = false;
+
+void crack_publish_stats(const dwpa_crack_stats& st, const std::vector<dwpa_crack_worker>& workers) {
+    g_last_stats = st;
+    g_last_workers = workers;
+    g_have_stats = true;
+}
+
+// One m22000 line per line (LF or CRLF), empty lines dropped.
+bool read_hash_file(const char* path, std::vector<std::string>& lines) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return false;
+    std::string cur;
+    int ch;
+    while ((ch = fgetc(f)) != EOF) {
+        if (ch == '\n') {
+            if (!cur.empty() && cur.back() == '\r') cur.pop_back();
+            if (!cur.empty()) lines.push_back(cur);
+            cur.clear();
+        } else cur.push_back((char)ch);
+    }
+    if (!cur.empty() && cur.back() == '\r') cur.pop_back();
+    if (!cur.empty()) lines.push_back(cur);
+    fclose(f);
+    return true;
+}
 
 static bool trace_on() {
     const char* e = getenv("DWPA_TRACE");
@@ -224,24 +249,8 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
     if (devs.empty()) return DWPA_RC_ERROR;
     const int nc_mode = DWPA_CFG_HAS(cfg, nc_mode) ? cfg->nc_mode : DWPA_NC_HASHCAT;
 
-    // hash file
     std::vector<std::string> lines;
-    {
-        FILE* f = fopen(hash_file, "rb");
-        if (!f) return DWPA_RC_ERROR;
-        std::string cur;
-        int ch;
-        while ((ch = fgetc(f)) != EOF) {
-            if (ch == '\n') {
-                if (!cur.empty() && cur.back() == '\r') cur.pop_back();
-                if (!cur.empty()) lines.push_back(cur);
-                cur.clear();
-            } else cur.push_back((char)ch);
-        }
-        if (!cur.empty() && cur.back() == '\r') cur.pop_back();
-        if (!cur.empty()) lines.push_back(cur);
-        fclose(f);
-    }
+    if (!read_hash_file(hash_file, lines)) return DWPA_RC_ERROR;
     CrackShared sh;
     sh.parsed.resize(lines.size());
     sh.cracked.assign(lines.size(), 0);
@@ -278,7 +287,7 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
     std::vector<size_t> ll(lines.size());
     for (size_t i = 0; i < lines.size(); i++) { lp[i] = lines[i].data(); ll[i] = lines[i].size(); }
     const uint32_t batch = DWPA_CFG_HAS(cfg, batch) && cfg->batch ? cfg->batch : engine_batch();
-    const size_t spd = shards_per_device();
+    const size_t spd = crack_shards_per_device();
     std::vector<std::unique_ptr<DevWork>> work;
     int rc = 0;
     for (int dev : devs)

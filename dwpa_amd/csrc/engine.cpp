@@ -33,6 +33,7 @@
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "m22000_host.hpp"
+#include "mask.hpp"
 
 namespace dwpa {
 
@@ -1472,6 +1473,11 @@ struct dwpa_scan {
     std::vector<Chunk> mg_chunks;
     std::vector<uint32_t> mg_gsalt_h, mg_list_h, mg_poff_h;
     dwpa::DevBuf mg_pmk, mg_gsalt, mg_list, mg_poff;
+    // dwpa_scan_set_mask: the parsed mask (host copy: dwpa_scan_load_mask decomposes `first` with it) and its device
+    // table (mask.hpp mask_table)
+    bool mask_set = false;
+    dwpa::Mask mask;
+    dwpa::DevBuf mask_tab;
 };
 
 namespace dwpa {
@@ -1540,6 +1546,7 @@ void scan_destroy(dwpa_scan* sc) {
     (void)hipDeviceSynchronize();
     sc->lines.release(); sc->atts.release(); sc->pool.release(); sc->salt.release(); sc->segs.release();
     sc->mg_pmk.release(); sc->mg_gsalt.release(); sc->mg_list.release(); sc->mg_poff.release();
+    sc->mask_tab.release();
     sc->batch.mid.release(); sc->batch.pmk.release(); sc->batch.ids.release(); sc->batch.hits.release();
     sc->batch.counters.release();
     delete sc;
@@ -1572,6 +1579,35 @@ int scan_load_numeric(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t di
     HIPCHK(launch_prep_numeric(first, count, digits, (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
                                sc->batch_cap, s));
     HIPCHK(hipStreamSynchronize(s));  // `count` lives on this host stack frame
+    return 0;
+}
+
+// A new mask replaces the previous one: launches that still read the old table are waited for first.
+int scan_set_mask(dwpa_scan* sc, const Mask& m) {
+    if (!sc || m.npos == 0 || m.npos > MASK_MAX_POS) return DWPA_E_ARG;
+    HIPCHK(hipSetDevice(sc->device));
+    std::vector<uint8_t> tab(MASK_TABLE_BYTES);
+    mask_table(m, tab.data());
+    HIPCHK(hipDeviceSynchronize());
+    sc->mask_set = false;
+    RCHK(sc->mask_tab.ensure(MASK_TABLE_BYTES));
+    HIPCHK(hipMemcpy(sc->mask_tab.p, tab.data(), MASK_TABLE_BYTES, hipMemcpyHostToDevice));
+    sc->mask = m;
+    sc->mask_set = true;
+    return 0;
+}
+
+// No host synchronisation: the digits of `first` travel in the kernel arguments and the kernel writes the loaded count.
+int scan_load_mask(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream) {
+    if (!sc || !sc->mask_set || count > sc->batch_cap) return DWPA_E_ARG;
+    const uint64_t K = sc->mask.keyspace;
+    if (first > K || count > K - first) return DWPA_E_ARG;  // first + count > K, also when the sum wraps
+    HIPCHK(hipSetDevice(sc->device));
+    uint8_t digits[64];
+    mask_digits(sc->mask, first < K ? first : 0, digits);  // first == K only with count 0: nothing is generated
+    HIPCHK(launch_prep_mask(digits, first, count, sc->mask.npos, (const uint8_t*)sc->mask_tab.p,
+                            (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p, (uint32_t*)sc->batch.counters.p,
+                            sc->batch_cap, as_stream(stream)));
     return 0;
 }
 
@@ -1957,6 +1993,26 @@ int dwpa_scan_load_dict(dwpa_scan* scan, const uint64_t* d_offsets, const uint8_
 int dwpa_scan_load_numeric(dwpa_scan* scan, uint64_t first, uint32_t count, uint32_t digits, void* hip_stream) {
     return guarded([&]() -> int {
         return scan_load_numeric(scan, first, count, digits, hip_stream);
+    });
+}
+int dwpa_scan_set_mask(dwpa_scan* scan, const char* mask, size_t mask_len, const dwpa_bytes custom[4],
+                       uint64_t* keyspace) {
+    return guarded([&]() -> int {
+        if (!scan) {  // no scan can exist without a device: say so first
+            RCHK(ensure_init());
+            return DWPA_E_ARG;
+        }
+        Mask m;
+        RCHK(mask_parse(mask, mask_len, custom, &m));
+        RCHK(scan_set_mask(scan, m));
+        if (keyspace) *keyspace = m.keyspace;
+        return 0;
+    });
+}
+int dwpa_scan_load_mask(dwpa_scan* scan, uint64_t first, uint32_t count, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!scan) RCHK(ensure_init());
+        return scan_load_mask(scan, first, count, hip_stream);
     });
 }
 int dwpa_scan_pbkdf2(dwpa_scan* scan, int group, void* hip_stream) {

@@ -5,6 +5,7 @@
 #include <functional>
 #include <new>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "dwpa22000.h"
@@ -94,6 +95,9 @@ int scan_counter_raw(dwpa_scan* sc, void* stream, uint32_t* raw);
 int scan_load_dict(dwpa_scan* sc, const uint64_t* off, const uint8_t* bytes, uint64_t first, uint32_t count,
                    uint32_t minlen, uint32_t maxlen, void* stream, bool fill = false);
 int scan_load_numeric(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t digits, void* stream);
+struct Mask;  // mask.hpp
+int scan_set_mask(dwpa_scan* sc, const Mask& m);
+int scan_load_mask(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream);
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream);
 int scan_verify(dwpa_scan* sc, int group, void* stream);
 int scan_run(dwpa_scan* sc, void* stream);
@@ -104,5 +108,14 @@ uint32_t scan_batch_cap(const dwpa_scan* sc);
 Batch& scan_batch_ref(dwpa_scan* sc);
 int scan_device(const dwpa_scan* sc);
 void scan_rules_drop(const dwpa_scan* scan);
+
+
+// crack.cpp helpers shared with crack_mask.cpp
+struct ParsedLine;  // m22000_host.hpp
+std::string outfile_record(const ParsedLine& p, const std::string& psk);
+size_t crack_shards_per_device();  // DWPA_CRACK_SHARDS_PER_DEVICE, 1..8
+bool read_hash_file(const char* path, std::vector<std::string>& lines);
+// what dwpa_crack_last_stats / dwpa_crack_worker_stats report for the calling thread from now on
+void crack_publish_stats(const dwpa_crack_stats& st, const std::vector<dwpa_crack_worker>& workers);
 
 }  // namespace dwpa

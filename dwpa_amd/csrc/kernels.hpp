@@ -17,6 +17,12 @@ hipError_t launch_prep_keys(const uint64_t* koff, const uint32_t* klen, const ui
                             uint32_t count, uint32_t* mid, uint32_t cap, hipStream_t s);
 hipError_t launch_prep_numeric(uint64_t first, uint32_t count, uint32_t digits, uint32_t* mid, uint64_t* ids,
                                uint32_t cap, hipStream_t s);
+// mask_dev.hip: mask candidates [first, first + count) -> midstates, ids[slot] = first + slot, *counter = count
+// (written by the kernel).  digits: the mixed-radix digits of `first` (mask_digits), table: the device copy of
+// mask_table (mask.hpp).  count <= cap.
+hipError_t launch_prep_mask(const uint8_t digits[64], uint64_t first, uint32_t count, uint32_t npos,
+                            const uint8_t* table, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
+                            hipStream_t s);
 // product launch: issue-pass code object (pbkdf2_module.cpp); DWPA_PBKDF2_PLAIN=1 -> launch_pbkdf2_plain
 // work (nullable): a 4-byte device counter the work-queue kernel may use (zeroed here before the launch)
 hipError_t launch_pbkdf2(const uint32_t* mid, uint32_t cap, uint32_t base, uint32_t count, const uint32_t* counter,

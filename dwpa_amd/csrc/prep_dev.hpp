@@ -1,4 +1,5 @@
-// prep_dev.hpp -- device helpers shared by the candidate-materialisation kernels (kernels.hip, rules.hip):
+// prep_dev.hpp -- device helpers shared by the candidate-materialisation kernels (kernels.hip, rules_dev.hip,
+// mask_dev.hip):
 // key bytes -> HMAC-SHA1 key block -> ipad/opad midstates, and wave-aggregated slot compaction.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -276,6 +276,70 @@ def crack_files_ex(hash_file, dicts, rules_file=None, nonce_error_corrections: i
     return rc, [int(st[i]) for i in range(len(dl))]
 
 
+def _custom(custom):
+    """custom sets ?1..?4 (bytes/str, None = undefined) -> (ctypes array of 4 Bytes, keep-alive)."""
+    custom = list(custom)
+    if len(custom) > 4:
+        raise L.DwpaError(L.DWPA_E_ARG, "at most four custom sets (?1..?4)")
+    return L.bytes_array([None if c is None else _b(c) for c in custom] + [None] * (4 - len(custom)))
+
+
+def _u64(v, what) -> int:
+    v = int(v)
+    if not 0 <= v < 2**64:
+        raise L.DwpaError(L.DWPA_E_ARG, f"{what} {v} is outside uint64")
+    return v
+
+
+def mask_keyspace(mask, custom=()) -> int:
+    """Keyspace of a hashcat -a 3 mask (host only): the product of its positions' set sizes.  custom: the sets
+    ?1..?4 as raw bytes in the mask language.  Raises DwpaError(DWPA_E_ARG) for an invalid mask or K > 2**64 - 1."""
+    m = _b(mask)
+    arr, keep = _custom(custom)
+    k = ctypes.c_uint64(0)
+    L.check(L.load().dwpa_mask_keyspace(m, len(m), arr, None, ctypes.byref(k)), "mask_keyspace")
+    return k.value
+
+
+def mask_positions(mask, custom=()) -> int:
+    """Positions (candidate length) of a mask (host only)."""
+    m = _b(mask)
+    arr, keep = _custom(custom)
+    n = ctypes.c_uint32(0)
+    L.check(L.load().dwpa_mask_keyspace(m, len(m), arr, ctypes.byref(n), None), "mask_keyspace")
+    return n.value
+
+
+def mask_candidate(mask, index: int, custom=()) -> bytes:
+    """Candidate `index` of a mask (host only), in the library's order: the mixed-radix numeral of the index with the
+    last position fastest (itertools.product order; hashcat's own order differs, the candidate set does not)."""
+    m = _b(mask)
+    arr, keep = _custom(custom)
+    out = ctypes.create_string_buffer(64)
+    n = ctypes.c_uint32(0)
+    L.check(L.load().dwpa_mask_candidate(m, len(m), arr, _u64(index, "index"), out, ctypes.byref(n)), "mask_candidate")
+    return out.raw[:n.value]
+
+
+def crack_mask(hash_file, mask, custom=(), skip: int = 0, limit: int = 0, increment=None,
+               nonce_error_corrections: int = 8, out_file="help_crack.key", device_mask: int = 0, batch: int = 0,
+               nc_mode: int = L.DWPA_NC_HASHCAT) -> int:
+    """In-process `hashcat -m22000 -a 3 hash_file mask`; returns a hashcat exit code (0 cracked, 1 exhausted,
+    -1 error).  skip / limit: indices [skip, skip + limit) of the keyspace in the library's order (limit 0 = to the
+    end).  increment: None = off, else (min, max) = the mask's prefixes of min..max positions, shortest first (not
+    with skip / limit).  Runs on every selected device."""
+    m = _b(mask)
+    if b"\0" in m:
+        raise L.DwpaError(L.DWPA_E_ARG, "crack_mask takes a NUL-terminated mask: put a NUL byte into a custom set")
+    arr, keep = _custom(custom)
+    imin, imax = (0, 0) if increment is None else (int(increment[0]), int(increment[1]))
+    if increment is not None and not (imin or imax):
+        imin = 1  # (0, 0) would mean "off" in the C call
+    cfg = L.Config(ctypes.sizeof(L.Config), device_mask, batch, nc_mode)
+    return L.load().dwpa_crack_mask(_b(hash_file), m, arr, _u64(skip, "skip"), _u64(limit, "limit"), imin, imax,
+                                    _nc(nonce_error_corrections), _b(out_file), ctypes.byref(cfg))
+
+
 def crack_stats():
     """dwpa_crack_last_stats: {words, candidates, hashes, cracked, seconds, rules, rules_skipped, rules_rejmem} of
     this thread's last crack call."""
@@ -335,6 +399,21 @@ class Scan:
 
     def load_numeric(self, first: int, count: int, digits: int = 8, stream: int = 0):
         L.check(self._lib.dwpa_scan_load_numeric(self._h, first, count, digits, stream), "scan_load_numeric")
+
+    def set_mask(self, mask, custom=()) -> int:
+        """Set the scan's hashcat -a 3 mask (custom: the sets ?1..?4 as raw bytes); returns its keyspace."""
+        m = _b(mask)
+        arr, keep = _custom(custom)
+        k = ctypes.c_uint64(0)
+        L.check(self._lib.dwpa_scan_set_mask(self._h, m, len(m), arr, ctypes.byref(k)), "scan_set_mask")
+        self.keyspace = k.value
+        return k.value
+
+    def load_mask(self, first: int, count: int, stream: int = 0):
+        """Mask candidates [first, first + count) into slots 0..count-1, generated on the GPU; candidate id = index."""
+        if not 0 <= int(count) < 2**32:
+            raise L.DwpaError(L.DWPA_E_ARG, f"count {count} is outside uint32")
+        L.check(self._lib.dwpa_scan_load_mask(self._h, _u64(first, "first"), int(count), stream), "scan_load_mask")
 
     def pbkdf2(self, group: int = 0, stream: int = 0):
         L.check(self._lib.dwpa_scan_pbkdf2(self._h, group, stream), "scan_pbkdf2")

@@ -1,0 +1,140 @@
+"""``python -m dwpa_amd.mask HASHFILE MASK`` -- hashcat's ``-m 22000 -a 3`` mask attack on libdwpa22000.so.
+
+It takes hashcat's spellings: ``-1``..``-4`` custom sets, ``-s/--skip``, ``-l/--limit``, ``-i --increment-min
+--increment-max``, ``-d`` (devices, numbered from 1), ``-o``, ``--nonce-error-corrections``.  The exit status is the
+call's return code (0 every hashline cracked, 1 exhausted, 255 error).  ``--keyspace`` and ``--stdout`` need no hash
+file and stay on the host.
+
+The candidates of a mask are hashcat's; their ORDER is the library's own (last position fastest, Python's
+``itertools.product`` order), so ``-s`` / ``-l`` windows do not name the candidates hashcat's windows name.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+from . import _lib as L
+from . import m22000 as M
+
+
+def _parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m dwpa_amd.mask", description=__doc__.split("\n\n")[0],
+                                formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("args", nargs="+", metavar="[HASHFILE] MASK",
+                   help="an m22000 hash file and a mask (?l ?u ?d ?h ?H ?s ?a ?b ?? ?1..?4, other bytes literal); "
+                        "the mask alone with --keyspace / --stdout")
+    for k in "1234":
+        p.add_argument("-" + k, "--custom-charset" + k, dest="c" + k, metavar="CS", help="custom set ?" + k)
+    p.add_argument("--hex-charset", action="store_true", help="the custom sets are given in hex")
+    p.add_argument("-s", "--skip", type=int, default=0, help="first index of the keyspace to run")
+    p.add_argument("-l", "--limit", type=int, default=0, help="number of indices to run (0: to the end)")
+    p.add_argument("-i", "--increment", action="store_true", help="run the mask's prefixes, shortest first")
+    p.add_argument("--increment-min", type=int, default=0, metavar="N")
+    p.add_argument("--increment-max", type=int, default=0, metavar="N")
+    p.add_argument("-d", "--backend-devices", default="", metavar="LIST", help="devices to use, numbered from 1: 1,2")
+    p.add_argument("-o", "--outfile", default="help_crack.key")
+    p.add_argument("--nonce-error-corrections", type=int, default=8, metavar="N")
+    p.add_argument("--batch", type=int, default=0, help="candidate slots per launch (0: the library's default)")
+    p.add_argument("--keyspace", action="store_true",
+                   help="print the mask's whole keyspace (the number of candidates) and exit.  hashcat prints a "
+                        "reduced figure for -a 3: the count its host loop steps through, without the part its "
+                        "kernels amplify")
+    p.add_argument("--stdout", action="store_true",
+                   help="write the candidates of [skip, skip + limit) to standard output, one per line as raw "
+                        "bytes, and exit")
+    return p
+
+
+def _fail(msg: str) -> int:
+    print("dwpa_amd.mask: " + msg, file=sys.stderr)
+    return 255
+
+
+def main(argv=None) -> int:
+    p = _parser()
+    try:
+        a = p.parse_args(argv)
+    except SystemExit as e:  # argparse: 0 after --help, 2 for bad arguments
+        return 0 if e.code in (0, None) else 255
+    host_only = a.keyspace or a.stdout
+    if not (len(a.args) == 2 or (host_only and len(a.args) == 1)):
+        return _fail("expected HASHFILE MASK" + (" or MASK" if host_only else ""))
+    mask = os.fsencode(a.args[-1])
+    custom = []
+    for k in "1234":
+        c = getattr(a, "c" + k)
+        if c is None:
+            custom.append(None)
+        elif a.hex_charset:
+            try:
+                custom.append(bytes.fromhex(c))
+            except ValueError:
+                return _fail(f"-{k}: not hex")
+        else:
+            custom.append(os.fsencode(c))
+    increment = None
+    if a.increment:
+        increment = (a.increment_min or 1, a.increment_max)
+    elif a.increment_min or a.increment_max:
+        return _fail("--increment-min / --increment-max need -i")
+    if a.skip < 0 or a.limit < 0 or a.increment_min < 0 or a.increment_max < 0:
+        return _fail("negative argument")
+    if increment and increment[1] and increment[0] > increment[1]:
+        return _fail("--increment-min is above --increment-max")
+    if increment and (a.skip or a.limit):
+        return _fail("--increment cannot be combined with --skip / --limit")
+    try:
+        npos = M.mask_positions(mask, custom)
+        keyspace = M.mask_keyspace(mask, custom)
+        if host_only:
+            if increment:
+                lo, hi = increment[0], min(increment[1] or npos, npos)
+                if lo > hi:
+                    return _fail("--increment-min is above the mask's length")
+                masks = [_prefix(mask, n) for n in range(lo, hi + 1)]
+            else:
+                masks = [mask]
+            if a.keyspace:
+                print(sum(M.mask_keyspace(m, custom) for m in masks))
+                return 0
+            out = sys.stdout.buffer
+            for m in masks:
+                k = M.mask_keyspace(m, custom)
+                if a.skip >= k:
+                    return _fail("--skip is not below the keyspace")
+                for i in range(a.skip, min(k, a.skip + a.limit) if a.limit else k):
+                    out.write(M.mask_candidate(m, i, custom) + b"\n")
+            out.flush()
+            return 0
+        devices = 0
+        for d in a.backend_devices.split(","):
+            if d.strip():
+                if not d.strip().isdigit() or int(d) < 1 or int(d) > 32:
+                    return _fail("-d takes device numbers from 1")
+                devices |= 1 << (int(d) - 1)
+        if not increment and a.skip >= keyspace:
+            return _fail("--skip is not below the keyspace")
+        rc = M.crack_mask(a.args[0], mask, custom, a.skip, a.limit, increment, a.nonce_error_corrections, a.outfile,
+                          device_mask=devices, batch=a.batch)
+    except L.DwpaError as e:
+        return _fail(str(e))
+    if rc in (0, 1):
+        st = M.crack_stats()
+        print("dwpa_amd.mask: %s, %d/%d hashlines cracked, %d candidates in %.1f s" %
+              ("cracked" if rc == 0 else "exhausted", st["cracked"], st["hashes"], st["candidates"], st["seconds"]),
+              file=sys.stderr)
+        return rc
+    return _fail("crack_mask failed")
+
+
+def _prefix(mask: bytes, n: int) -> bytes:
+    """The mask text of the first n positions."""
+    i = 0
+    for _ in range(n):
+        i += 2 if mask[i:i + 1] == b"?" else 1
+    return mask[:i]
+
+
+if __name__ == "__main__":
+    sys.exit(main())

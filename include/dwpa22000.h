@@ -39,7 +39,10 @@ extern "C" {
 
 #define DWPA_ABI_VERSION 4   /* 2: dwpa_crack_stats.rules / rules_skipped, dwpa_rules_count; 3: dwpa_check_last_stats,
                                 dwpa_config.rule_mode, dwpa_rules_count_ex, dwpa_crack_stats.rules_rejmem; 4: the host
-                                backend -- dwpa_config.allow_cpu_fallback / host_max_pmks, dwpa_check_stats.backend */
+                                backend -- dwpa_config.allow_cpu_fallback / host_max_pmks, dwpa_check_stats.backend.
+                                Added since without a new version or error code, discoverable by symbol: the mask
+                                attack -- dwpa_mask_keyspace, dwpa_mask_candidate, dwpa_scan_set_mask,
+                                dwpa_scan_load_mask, dwpa_crack_mask */
 
 /* ---- return codes ------------------------------------------------------------------------------------------ */
 #define DWPA_MISS 0            /* no key matched (PHP: False)                                                 */
@@ -135,7 +138,7 @@ typedef struct {
 } dwpa_config;
 
 typedef struct {
-    uint64_t cand;             /* candidate id: dictionary word index, numeric value, or word*nrules+rule */
+    uint64_t cand;             /* candidate id: dictionary word index, numeric value / mask index, word*nrules+rule */
     uint32_t line;             /* index of the hashline in the scan's line array */
     int32_t nc;
     int8_t endian;
@@ -285,6 +288,42 @@ typedef struct {
 } dwpa_crack_worker;
 int dwpa_crack_worker_stats(dwpa_crack_worker *out, size_t cap, size_t *n);
 
+/* ---- mask attack: hashcat -a 3 ------------------------------------------------------------------------------
+ * The mask language is hashcat's: ?l a-z, ?u A-Z, ?d 0-9, ?h 0-9a-f, ?H 0-9A-F, ?s the 33 ASCII specials in byte
+ * order (0x20-0x2f, 0x3a-0x40, 0x5b-0x60, 0x7b-0x7e), ?a = ?l?u?d?s (95 bytes), ?b 0x00-0xff, ?? a literal '?',
+ * ?1..?4 the custom sets, any other byte a literal (a position of radix 1).  1..63 positions (63: m22000's longest
+ * PSK).  custom[k] is set ?(k+1) as raw bytes in the same language (so no --hex-charset is needed): built-in
+ * references, references to lower-numbered custom sets, ?? and literal bytes; duplicate bytes are dropped, the
+ * first occurrence kept, as hashcat does; ptr == NULL = undefined (custom itself may be NULL: none defined).
+ * Keyspace K = the product of the positions' set sizes, at most 2^64 - 1.
+ * Order -- this library's own: candidate i is the mixed-radix numeral of i with the LAST position fastest, i.e.
+ * Python's itertools.product order, and ?d x N at index v is dwpa_scan_load_numeric's candidate v.  Parity with
+ * hashcat is unpinned: hashcat walks a mask in Markov order, so its index i (and its --skip / --limit windows) names
+ * another candidate; the candidate SET of a mask is the same.
+ * DWPA_E_ARG: ?x with an unknown letter, a trailing lone '?', a reference to an undefined custom set (inside a custom
+ * set: to one not lower-numbered), an empty set, no position or more than 63, K above 2^64 - 1. */
+/* Host only (work without a device): positions and keyspace of a mask (either out pointer may be NULL) ... */
+int dwpa_mask_keyspace(const char *mask, size_t mask_len, const dwpa_bytes custom[4], uint32_t *positions,
+                       uint64_t *keyspace);
+/* ... and candidate `index` (< K, else DWPA_E_ARG): *out_len bytes in out, the rest of the 64 zeroed. */
+int dwpa_mask_candidate(const char *mask, size_t mask_len, const dwpa_bytes custom[4], uint64_t index,
+                        uint8_t out[64], uint32_t *out_len);
+/* hashcat -m 22000 -a 3 hash_file mask [-1..-4 custom] [-s skip -l limit | -i --increment-min --increment-max] -o
+ * out_file: dwpa_crack_files' hash file, outfile records (the PSK rebuilt on the host from the hit's index), return
+ * codes (DWPA_RC_*), nonce_error_corrections and cfg handling (nc_mode default hashcat).  mask is NUL-terminated.
+ * skip / limit select the indices [skip, skip + limit) of [0, K) in this library's order (limit 0 = to the end);
+ * skip >= K is DWPA_RC_ERROR, as hashcat refuses it.  increment_min / increment_max: 0 / 0 = off, else the call runs
+ * the mask's prefixes of increment_min..increment_max positions (clipped to the mask; a 0 bound = open), shortest
+ * first; combined with skip / limit it is DWPA_RC_ERROR, as in hashcat.  A mask length outside 8..63 is skipped with
+ * one stderr line, as hashcat skips it; nothing left to run is DWPA_RC_ERROR.
+ * Runs on every selected device (cfg->device_mask), DWPA_CRACK_SHARDS_PER_DEVICE workers per device: all workers take
+ * batch-sized ascending index ranges from one shared cursor and generate them on their device.
+ * dwpa_crack_last_stats afterwards: words 0, candidates as derived; dwpa_crack_worker_stats: one entry per worker
+ * (items = batches, words and wait_s 0).  Without a device: DWPA_RC_ERROR. */
+int dwpa_crack_mask(const char *hash_file, const char *mask, const dwpa_bytes custom[4], uint64_t skip, uint64_t limit,
+                    uint32_t increment_min, uint32_t increment_max, int nonce_error_corrections, const char *out_file,
+                    const dwpa_config *cfg);
+
 /* hashcat rules (the whole rule language of hashcat >= 6.2.6: every mangling, reject and memory function; one
  * rule per line, '#' comments; semantics in dwpa_amd/csrc/rules.hpp and oracle/rules.py).  The text entry points
  * below (dwpa_rules_expand, dwpa_rules_apply_host, dwpa_rules_count, dwpa_scan_set_rules) are the interpreter and
@@ -349,6 +388,14 @@ int dwpa_scan_load_rules(dwpa_scan *scan, const uint64_t *d_offsets, const uint8
                          uint32_t nwords, void *hip_stream);
 /* Decimal keyspace first..first+count-1, zero-padded to `digits` characters. */
 int dwpa_scan_load_numeric(dwpa_scan *scan, uint64_t first, uint32_t count, uint32_t digits, void *hip_stream);
+/* Mask keyspace (the language and the order: "mask attack" above), generated in-kernel.  Set the scan's mask once
+ * (uploads one 16 KiB table; setting it again replaces the previous one; *keyspace, nullable, receives K), then load
+ * candidates [first, first + count): candidate id = its index, slot s holds index first + s (no filter, no
+ * compaction), and dwpa_scan_loaded then equals count.  A load does not synchronise with the host.  DWPA_E_ARG:
+ * count > batch, first + count > K (also when the sum wraps), no mask set.  Without a device: DWPA_E_NODEV. */
+int dwpa_scan_set_mask(dwpa_scan *scan, const char *mask, size_t mask_len, const dwpa_bytes custom[4],
+                       uint64_t *keyspace);
+int dwpa_scan_load_mask(dwpa_scan *scan, uint64_t first, uint32_t count, void *hip_stream);
 /* Stages 2 and 3 for ESSID group g (PMKs of the loaded batch, then every uncracked line of that ESSID). */
 int dwpa_scan_pbkdf2(dwpa_scan *scan, int group, void *hip_stream);
 int dwpa_scan_verify(dwpa_scan *scan, int group, void *hip_stream);
