@@ -9,13 +9,16 @@ this package is its Python host side:
 * :class:`Scan`            -- device-resident scan of HBM dictionaries / keyspaces (client hot loop, bench)
 * :func:`crack_mask`       -- hashcat ``-a 3`` mask attack (``python -m dwpa_amd.mask`` is its command line);
   :func:`mask_keyspace` / :func:`mask_candidate` are its host-only helpers
+* :func:`crack_hybrid`     -- hashcat ``-a 6`` / ``-a 7`` hybrid attacks, wordlist + mask and mask + wordlist
+  (``python -m dwpa_amd.mask -a 6|7``); :meth:`Scan.load_hybrid` is their scan-path load
 * :mod:`dwpa_amd.help_crack` -- ``run_cracker`` replacement for help_crack.py
 """
-from ._lib import DwpaError, load  # noqa: F401
-from .m22000 import (BatchJobs, check_batch, check_key_m22000, crack_files, crack_mask, device_count,  # noqa: F401
-                     group_by_essid, mask_candidate, mask_keyspace, check_stats, hash_m22000, hc_unhex, init,
+from ._lib import DWPA_HYBRID_MASK_WORD, DWPA_HYBRID_WORD_MASK, DwpaError, load  # noqa: F401
+from .m22000 import (BatchJobs, check_batch, check_key_m22000, crack_files, crack_hybrid, crack_mask,  # noqa: F401
+                     device_count, group_by_essid, mask_candidate, mask_keyspace, check_stats, hash_m22000, hc_unhex, init,
                      parse_m22000, pbkdf2_pmk, rules_count, rules_count_ex, rules_expand, Scan)
 
 __all__ = ["DwpaError", "load", "BatchJobs", "check_key_m22000", "check_batch", "pbkdf2_pmk", "hc_unhex", "hash_m22000",
            "crack_files", "rules_count", "rules_count_ex", "check_stats", "rules_expand", "device_count", "Scan",
-           "parse_m22000", "group_by_essid", "init", "crack_mask", "mask_keyspace", "mask_candidate"]
+           "parse_m22000", "group_by_essid", "init", "crack_mask", "mask_keyspace", "mask_candidate",
+           "crack_hybrid", "DWPA_HYBRID_WORD_MASK", "DWPA_HYBRID_MASK_WORD"]

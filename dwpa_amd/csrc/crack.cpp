@@ -7,6 +7,8 @@
 // verify).  There is no device-to-device traffic: hits (a few bytes) are gathered on the host, where the first
 // hit of each hashline is written to the outfile and the line is retired on every device (hashcat reports each
 // hash once).  Rules (hashcat -r, help_crack.py:445-447,931-933) are applied on the GPU (rules.cpp).
+// dwpa_crack_hybrid() (hashcat -a 6 / -a 7) is the same call with a mask amplifying every word where the rule set
+// would: each word is joined with the mask's candidates on the GPU (hybrid_dev.hip).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -29,8 +31,17 @@
 #include "m22000_host.hpp"
 #include "dict_reader.hpp"
 #include "rules.hpp"
+#include "mask.hpp"
 
 namespace dwpa {
+
+// dwpa_crack_hybrid: the mask is the amplifier of every word, where the rule set is in a rules run.  valid = false:
+// the mask or the mode was refused (the call fails after it has marked unreadable dictionaries).
+struct HybridSpec {
+    const Mask* mask = nullptr;
+    int mode = 0;
+    bool valid = false;
+};
 
 struct CrackShared {
     std::mutex mu;
@@ -102,8 +113,67 @@ static void sync_retired(DevWork& w, CrackShared& sh) {
     w.seen_version = v;
 }
 
+// The first hit of each line (lowest candidate id first) is written to the outfile once and the line retired;
+// plain_of rebuilds a candidate's PSK on the host from its id.
+template <class F>
+static void report_hits(DevWork& w, CrackShared& sh, std::vector<HitDev>& hits, F&& plain_of) {
+    std::sort(hits.begin(), hits.end(), [](const HitDev& x, const HitDev& y) { return x.cand < y.cand; });
+    std::lock_guard<std::mutex> lk(sh.mu);
+    std::string plain;
+    for (const HitDev& h : hits) {
+        dwpa_hit ph;
+        hit_to_public(w.scan, h, ph);
+        if (sh.cracked[ph.line]) continue;
+        if (!plain_of(h.cand, &plain)) continue;
+        sh.cracked[ph.line] = 1;
+        sh.ncracked++;
+        sh.version.fetch_add(1, std::memory_order_acq_rel);
+        const std::string rec = outfile_record(sh.parsed[ph.line], plain);
+        fwrite(rec.data(), 1, rec.size(), sh.out);
+        fflush(sh.out);
+    }
+    if (sh.ncracked == sh.valid) sh.stop = true;
+}
+
+// A mask wider than the batch: one word x consecutive mask ranges of a batch each.  Whether a word survives the
+// 8..63 filter follows from its length alone, so a dropped word costs no launch.  Each word is loaded as word 0 of
+// the offsets from its own entry on: the ids are then the mask indices, whatever words * K would come to.
+static int scan_shard_wide(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, size_t e, const HybridSpec& hy,
+                           int slot) {
+    const uint32_t cap = scan_batch_cap(w.scan);
+    const uint64_t K = hy.mask->keyspace;
+    const uint32_t P = hy.mask->npos;
+    std::vector<HitDev> hits;
+    for (size_t wi = b; wi < e; wi++) {
+        const uint64_t L = c.off[wi + 1] - c.off[wi];
+        if (L > 63 || L + P < 8 || L + P > 63) continue;
+        for (uint64_t mf = 0; mf < K && !sh.stop.load(std::memory_order_relaxed); mf += cap) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(cap, K - mf);
+            int r;
+            if ((r = scan_load_hybrid(w.scan, (const uint64_t*)w.off[slot].p + (wi - b), (const uint8_t*)w.bytes[slot].p,
+                                      0, 1, mf, n, hy.mode, 8, 63, w.stream)) < 0)
+                return r;
+            sync_retired(w, sh);
+            if ((r = scan_run(w.scan, w.stream)) < 0) return r;
+            w.cands += n;
+            if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
+            if (hits.empty()) continue;
+            report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+                if (cand >= K) return false;
+                uint8_t m[64];
+                mask_candidate(*hy.mask, cand, m);
+                const std::string word(c.bytes.data() + c.off[wi], (size_t)L), ms((const char*)m, P);
+                *plain = hy.mode == DWPA_HYBRID_WORD_MASK ? word + ms : ms + word;
+                return true;
+            });
+        }
+        if (sh.stop.load(std::memory_order_relaxed)) break;
+    }
+    return 0;
+}
+
 static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, size_t e, const RuleSet* rules,
-                      int slot) {
+                      const HybridSpec* hy, int slot) {
     if (e <= b) return 0;
     if (hipSetDevice(w.device) != hipSuccess) return DWPA_E_HIP;
     if (hipStreamWaitEvent(w.stream, w.staged[slot], 0) != hipSuccess) return DWPA_E_HIP;
@@ -111,7 +181,9 @@ static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, siz
     const DevBuf& wbytes = w.bytes[slot];
     const uint32_t cap = scan_batch_cap(w.scan);
     const size_t words = e - b;
-    const uint64_t nrules = rules ? rules->size() : 1;
+    if (hy && hy->mask->keyspace > cap) return scan_shard_wide(w, sh, c, b, e, *hy, slot);
+    // a hybrid run's amplifier is its mask: K candidates per word where a rules run has nrules
+    const uint64_t nrules = hy ? hy->mask->keyspace : rules ? rules->size() : 1;
     // candidate id = word * nrules + rule; batches walk the candidate space in order.  Every PBKDF2 lane runs the
     // same 4096 iterations, so a batch costs ceil(candidates / 256K) wave rounds whatever its fill: the words per
     // batch follow the observed fraction of candidates that survive the 8..63 filter (and the rules), aiming at
@@ -121,10 +193,14 @@ static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, siz
     for (size_t wb = 0; wb < words && !sh.stop.load(std::memory_order_relaxed);) {
         // keep == 1 (nothing filtered so far): exactly one batch of candidates, which cannot overflow
         const double want = (keep >= 1.0 ? 1.0 : 0.995) * cap / ((double)nrules * keep);
-        const uint64_t most = 16ull * cap / nrules;  // kernel-side bound on a fill-mode load
+        // kernel-side bound on a fill-mode load (a hybrid load also stays below 2^32 lanes)
+        const uint64_t most = (hy ? std::min<uint64_t>(16ull * cap, UINT32_MAX) : 16ull * cap) / nrules;
         const uint32_t nw = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)want, most, words - wb}));
         int r;
-        if (rules)
+        if (hy)
+            r = scan_load_hybrid(w.scan, (const uint64_t*)woff.p, (const uint8_t*)wbytes.p, wb, nw, 0,
+                                 (uint32_t)nrules, hy->mode, 8, 63, w.stream, true);
+        else if (rules)
             r = rules_load(w.scan, &w.rules, (const uint64_t*)woff.p, (const uint8_t*)wbytes.p, wb, nw, w.stream, true);
         else
             r = scan_load_dict(w.scan, (const uint64_t*)woff.p, (const uint8_t*)wbytes.p, wb, nw, 8, 63, w.stream,
@@ -150,23 +226,18 @@ static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, siz
         std::vector<HitDev> hits;
         if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
         if (hits.empty()) continue;
-        std::sort(hits.begin(), hits.end(), [](const HitDev& x, const HitDev& y) { return x.cand < y.cand; });
-        std::lock_guard<std::mutex> lk(sh.mu);
-        for (const HitDev& h : hits) {
-            dwpa_hit ph;
-            hit_to_public(w.scan, h, ph);
-            if (sh.cracked[ph.line]) continue;
-            const uint64_t word = h.cand / nrules, rule = h.cand % nrules;
-            std::string plain(c.bytes.data() + c.off[b + word], c.off[b + word + 1] - c.off[b + word]);
-            if (rules && !rules->apply_host((size_t)rule, plain, &plain)) continue;  // cannot happen: the GPU kept it
-            sh.cracked[ph.line] = 1;
-            sh.ncracked++;
-            sh.version.fetch_add(1, std::memory_order_acq_rel);
-            const std::string rec = outfile_record(sh.parsed[ph.line], plain);
-            fwrite(rec.data(), 1, rec.size(), sh.out);
-            fflush(sh.out);
-        }
-        if (sh.ncracked == sh.valid) sh.stop = true;
+        report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+            const uint64_t word = cand / nrules, rule = cand % nrules;
+            plain->assign(c.bytes.data() + c.off[b + word], c.off[b + word + 1] - c.off[b + word]);
+            if (hy) {
+                uint8_t m[64];
+                mask_candidate(*hy->mask, rule, m);
+                const std::string ms((const char*)m, hy->mask->npos);
+                *plain = hy->mode == DWPA_HYBRID_WORD_MASK ? *plain + ms : ms + *plain;
+                return true;
+            }
+            return !rules || rules->apply_host((size_t)rule, *plain, plain);  // false cannot happen: the GPU kept it
+        });
     }
     return 0;
 }
@@ -216,7 +287,8 @@ static bool trace_on() {
 }
 
 static int crack_impl(const char* hash_file, const char* const* dicts, size_t ndicts, const char* rules_file, int nec,
-                      const char* out_file, const dwpa_config* cfg, int32_t* dict_status) {
+                      const char* out_file, const dwpa_config* cfg, int32_t* dict_status,
+                      const HybridSpec* hy = nullptr) {
     const auto t_call = std::chrono::steady_clock::now();
     g_last_stats = dwpa_crack_stats{};  // an early return reports zeros, never the previous call
     g_last_workers.clear();
@@ -242,7 +314,7 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
             fclose(f);
         }
     }
-    if (unreadable) return DWPA_RC_ERROR;
+    if (unreadable || (hy && !hy->valid)) return DWPA_RC_ERROR;
     // the config applies to this call only (dwpa_init's process-wide selection stays as it is)
     if (engine_init() < 0) return DWPA_RC_ERROR;
     std::vector<int> devs = engine_devices(DWPA_CFG_HAS(cfg, device_mask) ? cfg->device_mask : 0);
@@ -303,6 +375,7 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
                 rc = DWPA_E_HIP;
             if (rc >= 0) rc = scan_create(dev, lp.data(), ll.data(), lines.size(), nec, nc_mode, batch, &w.scan);
             if (rc >= 0 && rp) rc = rules_upload(dev, rules, &w.rules);
+            if (rc >= 0 && hy) rc = scan_set_mask(w.scan, *hy->mask);
         }
     const size_t G = work.size();
 
@@ -313,7 +386,9 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
     // 16 batches (a partial last batch per item then costs ~1 % of its wave rounds).  The reader's chunks start at
     // one item per worker and grow to two full items per worker, so reading stays ahead of the scans without
     // holding much more than that in memory.
-    const size_t nr = rp ? rp->size() : 1;
+    // A hybrid run divides by its mask's keyspace K: K = 1 sizes items as a plain dictionary run does; K above the
+    // batch makes every item one word (first_item = most_item = 1), which is K / batch launches.
+    const size_t nr = hy ? (size_t)hy->mask->keyspace : rp ? rp->size() : 1;
     const size_t first_item = std::max<size_t>(1, batch / nr / 16), most_item = std::max<size_t>(1, 16 * (size_t)batch / nr);
     ChunkSource source(dpaths, first_item * G, 2 * most_item * G);
     // several workers: items of at most 2 batches, so an item handed out just before the readers reach the end
@@ -380,7 +455,7 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
                         it = w.slot_item[slot];
                     }
                     const auto ts = std::chrono::steady_clock::now();
-                    const int r = guarded([&] { return scan_shard(w, sh, *it.chunk, it.b, it.e, rp, slot); });
+                    const int r = guarded([&] { return scan_shard(w, sh, *it.chunk, it.b, it.e, rp, hy, slot); });
                     w.scan_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
                     w.items++;
                     w.words += it.e - it.b;
@@ -654,6 +729,29 @@ int dwpa_crack_files_ex(const char* hash_file, const char* const* dicts, size_t 
                         int32_t* dict_status) {
     return dwpa::guarded([&]() -> int {
         return dwpa::crack_impl(hash_file, dicts, ndicts, rules_file, nonce_error_corrections, out_file, cfg, dict_status);
+    }, DWPA_RC_ERROR, DWPA_RC_ERROR);
+}
+
+int dwpa_crack_hybrid(const char* hash_file, const char* const* dicts, size_t ndicts, const char* mask,
+                      const dwpa_bytes custom[4], int mode, int nonce_error_corrections, const char* out_file,
+                      const dwpa_config* cfg, int32_t* dict_status) {
+    return dwpa::guarded([&]() -> int {
+        auto m = std::make_unique<dwpa::Mask>();
+        dwpa::HybridSpec hy;
+        hy.mask = m.get();
+        hy.mode = mode;
+        hy.valid = true;
+        if (mode != DWPA_HYBRID_WORD_MASK && mode != DWPA_HYBRID_MASK_WORD) {
+            fprintf(stderr, "[dwpa] hybrid mode %d: 6 (wordlist + mask) or 7 (mask + wordlist)\n", mode);
+            hy.valid = false;
+        }
+        if (!mask || dwpa::mask_parse(mask, strlen(mask), custom, m.get()) < 0) {
+            fprintf(stderr, "[dwpa] mask %s: invalid (syntax, an undefined custom set, more than 63 positions or a "
+                            "keyspace above 2^64 - 1)\n", mask ? mask : "(null)");
+            hy.valid = false;
+        }
+        return dwpa::crack_impl(hash_file, dicts, ndicts, nullptr, nonce_error_corrections, out_file, cfg, dict_status,
+                                &hy);
     }, DWPA_RC_ERROR, DWPA_RC_ERROR);
 }
 

@@ -1611,6 +1611,32 @@ int scan_load_mask(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream) 
     return 0;
 }
 
+// Words x the scan's mask (hybrid_dev.hip).  The counter is zeroed on the stream and counted up by the kernel, as in
+// scan_load_dict; fill = true (crack_hybrid): up to 16 batches of raw candidates, the caller reads the raw count.
+int scan_load_hybrid(dwpa_scan* sc, const uint64_t* off, const uint8_t* bytes, uint64_t first_word, uint32_t nwords,
+                     uint64_t mask_first, uint32_t mask_count, int mode, uint32_t minlen, uint32_t maxlen,
+                     void* stream, bool fill) {
+    if (!sc || !sc->mask_set || (mode != DWPA_HYBRID_WORD_MASK && mode != DWPA_HYBRID_MASK_WORD)) return DWPA_E_ARG;
+    const uint64_t K = sc->mask.keyspace;
+    const uint64_t most = fill ? std::min<uint64_t>(16 * (uint64_t)sc->batch_cap, UINT32_MAX) : sc->batch_cap;
+    if ((uint64_t)nwords * mask_count > most) return DWPA_E_ARG;
+    if (mask_first > K || mask_count > K - mask_first) return DWPA_E_ARG;  // mask_first + mask_count > K, wrap included
+    uint64_t last_word, last_id;
+    if (__builtin_add_overflow(first_word, (uint64_t)nwords, &last_word) ||
+        __builtin_mul_overflow(last_word, K, &last_id))
+        return DWPA_E_ARG;  // ids are word_index * K + mask_index in 64 bits
+    HIPCHK(hipSetDevice(sc->device));
+    hipStream_t s = as_stream(stream);
+    HIPCHK(hipMemsetAsync(sc->batch.counters.p, 0, 4, s));
+    uint8_t digits[64];
+    mask_digits(sc->mask, mask_first < K ? mask_first : 0, digits);  // mask_first == K only with mask_count 0
+    HIPCHK(launch_prep_hybrid(digits, off, bytes, first_word, nwords, mask_first, mask_count, K, sc->mask.npos,
+                              mode == DWPA_HYBRID_MASK_WORD, minlen, maxlen, (const uint8_t*)sc->mask_tab.p,
+                              (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
+                              (uint32_t*)sc->batch.counters.p, sc->batch_cap, s));
+    return 0;
+}
+
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream) {
     if (!sc || group < 0 || group >= (int)sc->groups.size()) return DWPA_E_ARG;
     HIPCHK(hipSetDevice(sc->device));
@@ -2013,6 +2039,15 @@ int dwpa_scan_load_mask(dwpa_scan* scan, uint64_t first, uint32_t count, void* h
     return guarded([&]() -> int {
         if (!scan) RCHK(ensure_init());
         return scan_load_mask(scan, first, count, hip_stream);
+    });
+}
+int dwpa_scan_load_hybrid(dwpa_scan* scan, const uint64_t* d_offsets, const uint8_t* d_bytes, uint64_t first_word,
+                          uint32_t nwords, uint64_t mask_first, uint32_t mask_count, int mode, uint32_t minlen,
+                          uint32_t maxlen, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!scan) RCHK(ensure_init());
+        return scan_load_hybrid(scan, d_offsets, d_bytes, first_word, nwords, mask_first, mask_count, mode, minlen,
+                                maxlen, hip_stream);
     });
 }
 int dwpa_scan_pbkdf2(dwpa_scan* scan, int group, void* hip_stream) {

@@ -98,6 +98,10 @@ int scan_load_numeric(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t di
 struct Mask;  // mask.hpp
 int scan_set_mask(dwpa_scan* sc, const Mask& m);
 int scan_load_mask(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream);
+// fill = true (crack_hybrid): nwords * mask_count may reach 16 batches (below 2^32), as for scan_load_dict
+int scan_load_hybrid(dwpa_scan* sc, const uint64_t* off, const uint8_t* bytes, uint64_t first_word, uint32_t nwords,
+                     uint64_t mask_first, uint32_t mask_count, int mode, uint32_t minlen, uint32_t maxlen,
+                     void* stream, bool fill = false);
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream);
 int scan_verify(dwpa_scan* sc, int group, void* stream);
 int scan_run(dwpa_scan* sc, void* stream);

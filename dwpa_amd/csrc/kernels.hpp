@@ -23,6 +23,15 @@ hipError_t launch_prep_numeric(uint64_t first, uint32_t count, uint32_t digits, 
 hipError_t launch_prep_mask(const uint8_t digits[64], uint64_t first, uint32_t count, uint32_t npos,
                             const uint8_t* table, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
                             hipStream_t s);
+// hybrid_dev.hip: words [first_word, first_word + nwords) of off/bytes x mask candidates [mask_first, mask_first +
+// mask_count), word-major, joined as word || mask or (mask_then_word) mask || word -> midstates in compacted slots;
+// kept iff len <= 63 and minlen <= len + npos <= min(maxlen, 64); ids[slot] = word * keyspace + mask index.  The
+// counter (zeroed by the caller) ends as the raw kept count, which may exceed cap.  nwords * mask_count < 2^32.
+hipError_t launch_prep_hybrid(const uint8_t digits[64], const uint64_t* off, const uint8_t* bytes, uint64_t first_word,
+                              uint32_t nwords, uint64_t mask_first, uint32_t mask_count, uint64_t keyspace,
+                              uint32_t npos, bool mask_then_word, uint32_t minlen, uint32_t maxlen,
+                              const uint8_t* table, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
+                              hipStream_t s);
 // product launch: issue-pass code object (pbkdf2_module.cpp); DWPA_PBKDF2_PLAIN=1 -> launch_pbkdf2_plain
 // work (nullable): a 4-byte device counter the work-queue kernel may use (zeroed here before the launch)
 hipError_t launch_pbkdf2(const uint32_t* mid, uint32_t cap, uint32_t base, uint32_t count, const uint32_t* counter,

@@ -1,5 +1,5 @@
 // prep_dev.hpp -- device helpers shared by the candidate-materialisation kernels (kernels.hip, rules_dev.hip,
-// mask_dev.hip):
+// mask_dev.hip, hybrid_dev.hip):
 // key bytes -> HMAC-SHA1 key block -> ipad/opad midstates, and wave-aggregated slot compaction.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -340,6 +340,26 @@ def crack_mask(hash_file, mask, custom=(), skip: int = 0, limit: int = 0, increm
                                     _nc(nonce_error_corrections), _b(out_file), ctypes.byref(cfg))
 
 
+def crack_hybrid(hash_file, dicts, mask, custom=(), mode: int = L.DWPA_HYBRID_WORD_MASK,
+                 nonce_error_corrections: int = 8, out_file="help_crack.key", device_mask: int = 0, batch: int = 0,
+                 nc_mode: int = L.DWPA_NC_HASHCAT):
+    """In-process `hashcat -m22000 -a 6 hash_file dicts... mask` (mode 6: word + mask candidate) or `-a 7 hash_file
+    mask dicts...` (mode 7: mask candidate + word) over plain or gzip dictionaries, on every selected device.
+    Returns (rc, dict_status): a hashcat exit code (0 cracked, 1 exhausted, -1 error) and one status per dictionary
+    (DWPA_DICT_OK | DWPA_DICT_DAMAGED | DWPA_E_IO)."""
+    m = _b(mask)
+    if b"\0" in m:
+        raise L.DwpaError(L.DWPA_E_ARG, "crack_hybrid takes a NUL-terminated mask: put a NUL byte into a custom set")
+    arr, keep = _custom(custom)
+    cfg = L.Config(ctypes.sizeof(L.Config), device_mask, batch, nc_mode)
+    dl = [_b(d) for d in dicts]
+    darr = (ctypes.c_char_p * max(1, len(dl)))(*dl)
+    st = (ctypes.c_int32 * max(1, len(dl)))()
+    rc = L.load().dwpa_crack_hybrid(_b(hash_file), darr, len(dl), m, arr, int(mode), _nc(nonce_error_corrections),
+                                    _b(out_file), ctypes.byref(cfg), st)
+    return rc, [int(st[i]) for i in range(len(dl))]
+
+
 def crack_stats():
     """dwpa_crack_last_stats: {words, candidates, hashes, cracked, seconds, rules, rules_skipped, rules_rejmem} of
     this thread's last crack call."""
@@ -414,6 +434,18 @@ class Scan:
         if not 0 <= int(count) < 2**32:
             raise L.DwpaError(L.DWPA_E_ARG, f"count {count} is outside uint32")
         L.check(self._lib.dwpa_scan_load_mask(self._h, _u64(first, "first"), int(count), stream), "scan_load_mask")
+
+    def load_hybrid(self, d_offsets: int, d_bytes: int, first_word: int, nwords: int, mask_first: int, mask_count: int,
+                    mode: int = L.DWPA_HYBRID_WORD_MASK, minlen=8, maxlen=63, stream: int = 0):
+        """Words [first_word, first_word + nwords) x indices [mask_first, mask_first + mask_count) of the mask set by
+        set_mask, joined as word + mask candidate (mode 6) or mask candidate + word (mode 7) on the GPU.  Words whose
+        joined length is outside minlen..maxlen leave no slots; candidate id = word index * keyspace + mask index."""
+        for v, what in ((nwords, "nwords"), (mask_count, "mask_count"), (minlen, "minlen"), (maxlen, "maxlen")):
+            if not 0 <= int(v) < 2**32:
+                raise L.DwpaError(L.DWPA_E_ARG, f"{what} {v} is outside uint32")
+        L.check(self._lib.dwpa_scan_load_hybrid(self._h, d_offsets, d_bytes, _u64(first_word, "first_word"),
+                                                int(nwords), _u64(mask_first, "mask_first"), int(mask_count),
+                                                int(mode), int(minlen), int(maxlen), stream), "scan_load_hybrid")
 
     def pbkdf2(self, group: int = 0, stream: int = 0):
         L.check(self._lib.dwpa_scan_pbkdf2(self._h, group, stream), "scan_pbkdf2")

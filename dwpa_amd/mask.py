@@ -1,9 +1,15 @@
-"""``python -m dwpa_amd.mask HASHFILE MASK`` -- hashcat's ``-m 22000 -a 3`` mask attack on libdwpa22000.so.
+"""``python -m dwpa_amd.mask HASHFILE MASK`` -- hashcat's ``-m 22000 -a 3`` mask attack on libdwpa22000.so, and its
+hybrid attacks ``-a 6 HASHFILE DICT [DICT...] MASK`` (word + mask) and ``-a 7 HASHFILE MASK DICT [DICT...]`` (mask +
+word).
 
 It takes hashcat's spellings: ``-1``..``-4`` custom sets, ``-s/--skip``, ``-l/--limit``, ``-i --increment-min
 --increment-max``, ``-d`` (devices, numbered from 1), ``-o``, ``--nonce-error-corrections``.  The exit status is the
 call's return code (0 every hashline cracked, 1 exhausted, 255 error).  ``--keyspace`` and ``--stdout`` need no hash
 file and stay on the host.
+
+With ``-a 6`` / ``-a 7`` the dictionaries are plain or gzip wordlists (``$HEX[]`` words decoded); ``--stdout`` then
+takes no hash file (``-a 6 --stdout DICT... MASK``) and prints every word x mask candidate, unfiltered, word-major
+with the mask index fastest.  ``-s``, ``-l``, ``-i`` and ``--keyspace`` belong to ``-a 3`` only.
 
 The candidates of a mask are hashcat's; their ORDER is the library's own (last position fastest, Python's
 ``itertools.product`` order), so ``-s`` / ``-l`` windows do not name the candidates hashcat's windows name.
@@ -11,6 +17,7 @@ The candidates of a mask are hashcat's; their ORDER is the library's own (last p
 from __future__ import annotations
 
 import argparse
+import gzip
 import os
 import sys
 
@@ -24,6 +31,9 @@ def _parser() -> argparse.ArgumentParser:
     p.add_argument("args", nargs="+", metavar="[HASHFILE] MASK",
                    help="an m22000 hash file and a mask (?l ?u ?d ?h ?H ?s ?a ?b ?? ?1..?4, other bytes literal); "
                         "the mask alone with --keyspace / --stdout")
+    p.add_argument("-a", "--attack-mode", type=int, default=3, metavar="N",
+                   help="3 mask (default); 6 wordlist + mask: HASHFILE DICT [DICT...] MASK; 7 mask + wordlist: "
+                        "HASHFILE MASK DICT [DICT...]")
     for k in "1234":
         p.add_argument("-" + k, "--custom-charset" + k, dest="c" + k, metavar="CS", help="custom set ?" + k)
     p.add_argument("--hex-charset", action="store_true", help="the custom sets are given in hex")
@@ -57,22 +67,17 @@ def main(argv=None) -> int:
         a = p.parse_args(argv)
     except SystemExit as e:  # argparse: 0 after --help, 2 for bad arguments
         return 0 if e.code in (0, None) else 255
+    if a.attack_mode in (6, 7):
+        return _hybrid(a)
+    if a.attack_mode != 3:
+        return _fail("-a takes 3 (mask), 6 (wordlist + mask) or 7 (mask + wordlist)")
     host_only = a.keyspace or a.stdout
     if not (len(a.args) == 2 or (host_only and len(a.args) == 1)):
         return _fail("expected HASHFILE MASK" + (" or MASK" if host_only else ""))
     mask = os.fsencode(a.args[-1])
-    custom = []
-    for k in "1234":
-        c = getattr(a, "c" + k)
-        if c is None:
-            custom.append(None)
-        elif a.hex_charset:
-            try:
-                custom.append(bytes.fromhex(c))
-            except ValueError:
-                return _fail(f"-{k}: not hex")
-        else:
-            custom.append(os.fsencode(c))
+    custom = _custom_sets(a)
+    if isinstance(custom, int):
+        return custom
     increment = None
     if a.increment:
         increment = (a.increment_min or 1, a.increment_max)
@@ -107,12 +112,9 @@ def main(argv=None) -> int:
                     out.write(M.mask_candidate(m, i, custom) + b"\n")
             out.flush()
             return 0
-        devices = 0
-        for d in a.backend_devices.split(","):
-            if d.strip():
-                if not d.strip().isdigit() or int(d) < 1 or int(d) > 32:
-                    return _fail("-d takes device numbers from 1")
-                devices |= 1 << (int(d) - 1)
+        devices = _devices(a)
+        if devices < 0:
+            return 255
         if not increment and a.skip >= keyspace:
             return _fail("--skip is not below the keyspace")
         rc = M.crack_mask(a.args[0], mask, custom, a.skip, a.limit, increment, a.nonce_error_corrections, a.outfile,
@@ -126,6 +128,97 @@ def main(argv=None) -> int:
               file=sys.stderr)
         return rc
     return _fail("crack_mask failed")
+
+
+def _custom_sets(a):
+    """The sets -1..-4 as bytes (None: not given), or the exit status after a message."""
+    custom = []
+    for k in "1234":
+        c = getattr(a, "c" + k)
+        if c is None:
+            custom.append(None)
+        elif a.hex_charset:
+            try:
+                custom.append(bytes.fromhex(c))
+            except ValueError:
+                return _fail(f"-{k}: not hex")
+        else:
+            custom.append(os.fsencode(c))
+    return custom
+
+
+def _devices(a) -> int:
+    """-d as a device mask (0: every device), or -1 after a message."""
+    devices = 0
+    for d in a.backend_devices.split(","):
+        if d.strip():
+            if not d.strip().isdigit() or int(d) < 1 or int(d) > 32:
+                _fail("-d takes device numbers from 1")
+                return -1
+            devices |= 1 << (int(d) - 1)
+    return devices
+
+
+def _words(path: str):
+    """The words of a wordlist as the library's reader cuts them: plain or gzip, one per line, "\\n" or "\\r\\n", a
+    last line without newline counted, empty lines kept, $HEX[] decoded."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:2] == b"\x1f\x8b":
+        data = gzip.decompress(data)
+    lines = data.split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    for w in lines:
+        if w.endswith(b"\r"):
+            w = w[:-1]
+        if len(w) > 5 and w.startswith(b"$HEX[") and w.endswith(b"]"):
+            w = M.hc_unhex(w)
+        yield w
+
+
+def _hybrid(a) -> int:
+    """-a 6 / -a 7: argument order as hashcat's, the mask last (6) or first (7) among the attack's operands."""
+    mode = a.attack_mode
+    if a.skip or a.limit or a.increment or a.increment_min or a.increment_max or a.keyspace:
+        return _fail(f"-s, -l, -i and --keyspace are not available with -a {mode}")
+    ops = a.args if a.stdout else a.args[1:]
+    if len(ops) < 2 or (not a.stdout and len(a.args) < 3):
+        return _fail(("expected " + ("" if a.stdout else "HASHFILE ")) +
+                     ("DICT [DICT...] MASK" if mode == 6 else "MASK DICT [DICT...]"))
+    mask = os.fsencode(ops[-1] if mode == 6 else ops[0])
+    dicts = ops[:-1] if mode == 6 else ops[1:]
+    custom = _custom_sets(a)
+    if isinstance(custom, int):
+        return custom
+    try:
+        keyspace = M.mask_keyspace(mask, custom)
+        for d in dicts:
+            if not os.path.isfile(d) or not os.access(d, os.R_OK):
+                return _fail(f"dictionary {d}: cannot be opened")
+        if a.stdout:
+            out = sys.stdout.buffer
+            for d in dicts:
+                for w in _words(d):
+                    for i in range(keyspace):
+                        m = M.mask_candidate(mask, i, custom)
+                        out.write((w + m if mode == 6 else m + w) + b"\n")
+            out.flush()
+            return 0
+        devices = _devices(a)
+        if devices < 0:
+            return 255
+        rc, status = M.crack_hybrid(a.args[0], dicts, mask, custom, mode, a.nonce_error_corrections, a.outfile,
+                                    device_mask=devices, batch=a.batch)
+    except (L.DwpaError, OSError) as e:
+        return _fail(str(e))
+    if rc in (0, 1):
+        st = M.crack_stats()
+        print("dwpa_amd.mask: %s, %d/%d hashlines cracked, %d words, %d candidates in %.1f s" %
+              ("cracked" if rc == 0 else "exhausted", st["cracked"], st["hashes"], st["words"], st["candidates"],
+               st["seconds"]), file=sys.stderr)
+        return rc
+    return _fail("crack_hybrid failed")
 
 
 def _prefix(mask: bytes, n: int) -> bytes:

@@ -42,7 +42,8 @@ extern "C" {
                                 backend -- dwpa_config.allow_cpu_fallback / host_max_pmks, dwpa_check_stats.backend.
                                 Added since without a new version or error code, discoverable by symbol: the mask
                                 attack -- dwpa_mask_keyspace, dwpa_mask_candidate, dwpa_scan_set_mask,
-                                dwpa_scan_load_mask, dwpa_crack_mask */
+                                dwpa_scan_load_mask, dwpa_crack_mask; the hybrid attacks -- dwpa_scan_load_hybrid,
+                                dwpa_crack_hybrid */
 
 /* ---- return codes ------------------------------------------------------------------------------------------ */
 #define DWPA_MISS 0            /* no key matched (PHP: False)                                                 */
@@ -324,6 +325,35 @@ int dwpa_crack_mask(const char *hash_file, const char *mask, const dwpa_bytes cu
                     uint32_t increment_min, uint32_t increment_max, int nonce_error_corrections, const char *out_file,
                     const dwpa_config *cfg);
 
+/* ---- hybrid attacks: hashcat -a 6 (wordlist || mask) and -a 7 (mask || wordlist) ------------------------------
+ * Candidate: mode 6 = word || m, mode 7 = m || word, m a candidate of the mask (the mask language above, 1..63
+ * positions, keyspace K).
+ * Order and id -- word-major, mask index fastest: id = word_index * K + mask_index, word_index indexing the words as
+ * handed over (the d_offsets array of a scan load, as dwpa_scan_load_dict's ids do), mask_index in this library's own
+ * mask order (last position fastest).  Parity with hashcat's order is unpinned, as for -a 3; the candidate set is
+ * the same.
+ * Filter: a word of L bytes with a mask of P positions is kept iff minlen <= L + P <= maxlen (the crack call uses
+ * 8..63; a scan load treats maxlen above 64 as 64, one HMAC key block).  All K candidates of a word are kept or
+ * dropped together.  An empty word is an ordinary word, kept when P >= minlen (parity with hashcat for empty lines is
+ * unpinned).  Words longer than 63 bytes always drop.  Dropped words leave no slots. */
+#define DWPA_HYBRID_WORD_MASK 6
+#define DWPA_HYBRID_MASK_WORD 7
+/* hashcat -m 22000 -a 6 hash_file dicts... mask / -a 7 hash_file mask dicts... [-1..-4 custom] -o out_file, with
+ * everything dwpa_crack_files_ex does for a dictionary run: hash file, outfile records (the PSK rebuilt on the host
+ * from the word and the mask index), return codes, nonce_error_corrections, cfg (nc_mode default hashcat), plain or
+ * gzip dictionaries with $HEX[] words, dict_status (nullable, one per dictionary), every selected device with
+ * DWPA_CRACK_SHARDS_PER_DEVICE workers each, stop when every line is cracked.  mask is NUL-terminated; mode is
+ * DWPA_HYBRID_WORD_MASK or DWPA_HYBRID_MASK_WORD.  K <= batch: a launch holds whole words x the whole mask; K > batch:
+ * one word x consecutive mask ranges of `batch` (a word the filter drops costs no launch).
+ * DWPA_RC_ERROR before any device is touched: an invalid mask, an unknown mode, an unreadable dictionary (its
+ * dict_status is DWPA_E_IO, whatever else is wrong with the call).  A mask that no word can complete to 8..63
+ * characters (P > 63 cannot be written; P = 63 keeps only empty words) simply exhausts.
+ * dwpa_crack_last_stats afterwards: words = words read, candidates = kept words x K derived;
+ * dwpa_crack_worker_stats as for dwpa_crack_files. */
+int dwpa_crack_hybrid(const char *hash_file, const char *const *dicts, size_t ndicts, const char *mask,
+                      const dwpa_bytes custom[4], int mode, int nonce_error_corrections, const char *out_file,
+                      const dwpa_config *cfg, int32_t *dict_status /* nullable */);
+
 /* hashcat rules (the whole rule language of hashcat >= 6.2.6: every mangling, reject and memory function; one
  * rule per line, '#' comments; semantics in dwpa_amd/csrc/rules.hpp and oracle/rules.py).  The text entry points
  * below (dwpa_rules_expand, dwpa_rules_apply_host, dwpa_rules_count, dwpa_scan_set_rules) are the interpreter and
@@ -396,6 +426,16 @@ int dwpa_scan_load_numeric(dwpa_scan *scan, uint64_t first, uint32_t count, uint
 int dwpa_scan_set_mask(dwpa_scan *scan, const char *mask, size_t mask_len, const dwpa_bytes custom[4],
                        uint64_t *keyspace);
 int dwpa_scan_load_mask(dwpa_scan *scan, uint64_t first, uint32_t count, void *hip_stream);
+/* Hybrid candidates ("hybrid attacks" above) of words [first_word, first_word + nwords) of an HBM-resident dictionary
+ * (d_offsets: at least first_word + nwords + 1 offsets) x the indices [mask_first, mask_first + mask_count) of the
+ * mask set by dwpa_scan_set_mask, word-major: nwords * mask_count raw candidates, the kept ones compacted into slots
+ * in that order, ids[slot] = word_index * K + mask_index, dwpa_scan_loaded = the kept count.  A load does not
+ * synchronise with the host.  DWPA_E_ARG (the scan stays usable): no mask set, mode not 6 or 7, nwords * mask_count >
+ * batch, mask_first + mask_count > K (wrap included), (first_word + nwords) * K beyond 64 bits.  Without a device:
+ * DWPA_E_NODEV. */
+int dwpa_scan_load_hybrid(dwpa_scan *scan, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t first_word,
+                          uint32_t nwords, uint64_t mask_first, uint32_t mask_count, int mode, uint32_t minlen,
+                          uint32_t maxlen, void *hip_stream);
 /* Stages 2 and 3 for ESSID group g (PMKs of the loaded batch, then every uncracked line of that ESSID). */
 int dwpa_scan_pbkdf2(dwpa_scan *scan, int group, void *hip_stream);
 int dwpa_scan_verify(dwpa_scan *scan, int group, void *hip_stream);
