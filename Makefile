@@ -8,7 +8,8 @@ LIB := dwpa_amd/lib/libdwpa22000.so
 HDRS := $(wildcard $(SRC)/*.hpp) include/dwpa22000.h
 OBJS := $(OBJ)/kernels.o $(OBJ)/rules_dev.o $(OBJ)/engine.o $(OBJ)/m22000_host.o $(OBJ)/crack.o $(OBJ)/rules.o \
         $(OBJ)/pbkdf2_module.o $(OBJ)/pbkdf2_hsaco.o $(OBJ)/host_crypto.o $(OBJ)/host_check.o \
-        $(OBJ)/mask.o $(OBJ)/mask_dev.o $(OBJ)/crack_mask.o $(OBJ)/hybrid_dev.o
+        $(OBJ)/mask.o $(OBJ)/mask_dev.o $(OBJ)/crack_mask.o $(OBJ)/hybrid_dev.o \
+        $(OBJ)/combi_dev.o
 LLVM := /opt/rocm/lib/llvm/bin
 ISSUE_RULE ?= sched=1:alt:orig:asmnop,before_half
 
@@ -56,11 +57,12 @@ $(LIB): $(OBJS)
 oracle:
 	$(MAKE) -s -C oracle
 
-asm: $(SRC)/kernels.hip $(SRC)/mask_dev.hip $(SRC)/hybrid_dev.hip $(HDRS)
+asm: $(SRC)/kernels.hip $(SRC)/mask_dev.hip $(SRC)/hybrid_dev.hip $(SRC)/combi_dev.hip $(HDRS)
 	@mkdir -p build/asm
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $< -o build/asm/kernels.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/mask_dev.hip -o build/asm/mask_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/hybrid_dev.hip -o build/asm/hybrid_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/combi_dev.hip -o build/asm/combi_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 
 clean:
 	rm -rf build $(LIB)

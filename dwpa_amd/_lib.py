@@ -21,6 +21,7 @@ DWPA_RC_CRACKED, DWPA_RC_EXHAUSTED, DWPA_RC_ERROR = 0, 1, -1
 DWPA_NC_PHP, DWPA_NC_HASHCAT = 0, 1
 DWPA_NC_MAX = 65664  # the largest nc / nonce_error_corrections taken (include/dwpa22000.h)
 DWPA_HYBRID_WORD_MASK, DWPA_HYBRID_MASK_WORD = 6, 7  # hashcat -a 6 (word || mask) / -a 7 (mask || word)
+DWPA_COMBI_AMP_RIGHT, DWPA_COMBI_AMP_LEFT = 0, 1  # hashcat -a 1: the list held whole in device memory
 DWPA_DICT_OK, DWPA_DICT_DAMAGED = 0, 1  # dwpa_crack_files_ex per-dictionary status (or DWPA_E_IO)
 DWPA_RULES_DEFAULT, DWPA_RULES_HASHCAT, DWPA_RULES_FULL = 0, 1, 2  # dwpa_config.rule_mode
 DWPA_BACKEND_DEVICE, DWPA_BACKEND_HOST_SMALL, DWPA_BACKEND_HOST_FALLBACK = 0, 1, 2  # dwpa_check_stats.backend
@@ -149,6 +150,11 @@ SIGNATURES = {
     "dwpa_crack_hybrid": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_char_p,
                            ctypes.POINTER(Bytes), ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config),
                            ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "dwpa_scan_load_combinator": ([_P, _P, _P, ctypes.c_uint64, ctypes.c_uint32, _P, _P, ctypes.c_uint64,
+                                   ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, _P],
+                                  ctypes.c_int),
+    "dwpa_crack_combinator": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                               ctypes.c_char_p, ctypes.POINTER(Config), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "dwpa_crack_mask": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Bytes), ctypes.c_uint64, ctypes.c_uint64,
                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)],
                         ctypes.c_int),

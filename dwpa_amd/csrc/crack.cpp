@@ -9,6 +9,8 @@
 // hash once).  Rules (hashcat -r, help_crack.py:445-447,931-933) are applied on the GPU (rules.cpp).
 // dwpa_crack_hybrid() (hashcat -a 6 / -a 7) is the same call with a mask amplifying every word where the rule set
 // would: each word is joined with the mask's candidates on the GPU (hybrid_dev.hip).
+// dwpa_crack_combinator() (hashcat -a 1) is the same call again with a second word list as the amplifier: it lies
+// whole in device memory and every streamed word is joined with its words on the GPU (combi_dev.hip).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -43,6 +45,84 @@ struct HybridSpec {
     bool valid = false;
 };
 
+// dwpa_crack_combinator: one of the two lists is the amplifier of every word of the other (the base, which is
+// streamed as a dictionary run streams its words).  The amplifier is read whole into host memory once: it is uploaded
+// once per worker and kept here to rebuild a hit's PSK.  valid = false: the side was refused.
+struct CombiSpec {
+    int side = DWPA_COMBI_AMP_RIGHT;
+    bool valid = false;
+    std::vector<uint64_t> off{0};  // A + 1 offsets into bytes
+    std::string bytes;
+    int status = DWPA_DICT_OK;     // of the amplifier list (DWPA_DICT_DAMAGED: read up to the damage)
+    uint64_t below[65] = {};       // below[k]: amplifier words shorter than k bytes, k <= 64
+    // A > batch: range_below[r * 65 + k] = amplifier words before index r * range that are shorter than k bytes
+    std::vector<uint32_t> range_below;
+    uint64_t range = 0;
+
+    uint64_t words() const { return off.size() - 1; }
+    size_t base_index() const { return side == DWPA_COMBI_AMP_RIGHT ? 0 : 1; }  // of {left, right}
+    // The amplifier words that a base word of L bytes keeps have lo..hi bytes (8 <= L + R <= 63); false: none can.
+    static bool window(uint64_t L, uint32_t* lo, uint32_t* hi) {
+        if (L > 63) return false;
+        *lo = L < 8 ? 8 - (uint32_t)L : 0;
+        *hi = 63 - (uint32_t)L;
+        return true;
+    }
+    // kept pairs of a base word of L bytes x the whole amplifier: exact, from the amplifier's length histogram
+    uint64_t kept(uint64_t L) const {
+        uint32_t lo, hi;
+        return window(L, &lo, &hi) ? below[hi + 1] - below[lo] : 0;
+    }
+    // ... x amplifier range r, [r * range, (r + 1) * range)
+    uint64_t kept_in_range(uint64_t L, size_t r) const {
+        uint32_t lo, hi;
+        if (!window(L, &lo, &hi)) return 0;
+        const uint32_t* p = &range_below[r * 65];
+        return (uint64_t)(p[65 + hi + 1] - p[65 + lo]) - (p[hi + 1] - p[lo]);
+    }
+    void count_lengths() {
+        uint64_t hist[65] = {};
+        for (size_t i = 0; i + 1 < off.size(); i++) hist[std::min<uint64_t>(off[i + 1] - off[i], 64)]++;
+        below[0] = 0;
+        for (int k = 1; k <= 64; k++) below[k] = below[k - 1] + hist[k - 1];
+    }
+    void count_ranges(uint64_t cap) {
+        range = cap;
+        const uint64_t A = words();
+        const size_t R = (size_t)((A + cap - 1) / cap);
+        range_below.assign((R + 1) * 65, 0);
+        uint32_t hist[65] = {};  // words so far, by length
+        auto mark = [&](size_t r) {
+            uint32_t* p = &range_below[r * 65];
+            for (int k = 1; k <= 64; k++) p[k] = p[k - 1] + hist[k - 1];
+        };
+        for (uint64_t i = 0; i < A; i++) {
+            if (i % cap == 0) mark((size_t)(i / cap));
+            hist[std::min<uint64_t>(off[i + 1] - off[i], 64)]++;
+        }
+        mark(R);
+    }
+};
+
+// The amplifier list through the dictionary reader (plain or gzip, CRLF, $HEX[]), whole.  DWPA_E_IO: a read error;
+// DWPA_E_OVERFLOW: above the limit.
+static int read_amplifier(const char* path, CombiSpec* cb) {
+    DictReader rd({std::string(path)});
+    Chunk c;
+    bool err = false;
+    while (rd.next(c, (size_t)1 << 20, (size_t)64 << 20, err)) {
+        const uint64_t at = cb->bytes.size();
+        cb->bytes += c.bytes;
+        for (size_t i = 1; i < c.off.size(); i++) cb->off.push_back(at + c.off[i]);
+        if (cb->words() > UINT32_MAX || cb->bytes.size() + cb->off.size() * 8 > DWPA_COMBI_AMP_MAX_BYTES)
+            return DWPA_E_OVERFLOW;
+    }
+    if (err) return DWPA_E_IO;
+    if (rd.damaged()) cb->status = DWPA_DICT_DAMAGED;
+    cb->count_lengths();
+    return 0;
+}
+
 struct CrackShared {
     std::mutex mu;
     std::vector<uint8_t> cracked;         // per input line (1: cracked, or never usable)
@@ -67,6 +147,7 @@ struct DevWork {
     dwpa_scan* scan = nullptr;
     DevRules rules;
     DevBuf off[2], bytes[2];
+    DevBuf amp_off, amp_bytes;      // dwpa_crack_combinator: the amplifier list, uploaded once
     std::vector<uint64_t> hoff[2];  // host staging of the rebased offsets (alive until the upload completes)
     hipStream_t stream = nullptr, up = nullptr;
     hipEvent_t staged[2] = {nullptr, nullptr};
@@ -172,11 +253,114 @@ static int scan_shard_wide(DevWork& w, CrackShared& sh, const Chunk& c, size_t b
     return 0;
 }
 
+// The amplifier list of a combinator run, once per worker, with the 64 bytes of padding stage_shard gives.
+static int upload_amplifier(DevWork& w, const CombiSpec& cb) {
+    if (hipSetDevice(w.device) != hipSuccess) return DWPA_E_HIP;
+    if (w.amp_off.ensure(cb.off.size() * 8) || w.amp_bytes.ensure(cb.bytes.size() + 64)) return DWPA_E_NOMEM;
+    if (hipMemcpy(w.amp_off.p, cb.off.data(), cb.off.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        (!cb.bytes.empty() &&
+         hipMemcpy(w.amp_bytes.p, cb.bytes.data(), cb.bytes.size(), hipMemcpyHostToDevice) != hipSuccess))
+        return DWPA_E_HIP;
+    return 0;
+}
+
+// A combinator run's item: base words [b, e) of chunk c x the worker's amplifier list.  Nothing is sized by trial:
+// the host knows every length, so the kept pairs of a load follow from the amplifier's length counts (CombiSpec).
+//   A <= batch: nw whole base words x the whole amplifier, nw the most whose kept pairs fit the batch (and whose raw
+//               pairs fit a fill-mode load).  The kernel's own count is read back and must agree.
+//   A >  batch: one base word x consecutive amplifier ranges of a batch, as scan_shard_wide does; a word or a range
+//               that keeps no pair costs no launch.  The word is loaded as word 0 from its own offset, so the ids
+//               are the amplifier indices.
+static int scan_shard_combi(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, size_t e, const CombiSpec& cb,
+                            int slot) {
+    const uint32_t cap = scan_batch_cap(w.scan);
+    const uint64_t A = cb.words();
+    if (A == 0) return 0;
+    const uint64_t* boff = (const uint64_t*)w.off[slot].p;
+    const uint8_t* bbytes = (const uint8_t*)w.bytes[slot].p;
+    const uint64_t* aoff = (const uint64_t*)w.amp_off.p;
+    const uint8_t* abytes = (const uint8_t*)w.amp_bytes.p;
+    auto len_of = [&](size_t wi) { return c.off[wi + 1] - c.off[wi]; };
+    auto join = [&](size_t wi, uint64_t ai, std::string* plain) {
+        const std::string base(c.bytes.data() + c.off[wi], (size_t)len_of(wi));
+        const std::string amp(cb.bytes.data() + cb.off[ai], (size_t)(cb.off[ai + 1] - cb.off[ai]));
+        *plain = cb.side == DWPA_COMBI_AMP_LEFT ? amp + base : base + amp;
+    };
+    std::vector<HitDev> hits;
+    int r;
+    if (A > cap) {
+        const size_t R = (size_t)((A + cap - 1) / cap);
+        for (size_t wi = b; wi < e && !sh.stop.load(std::memory_order_relaxed); wi++) {
+            if (cb.kept(len_of(wi)) == 0) continue;
+            for (size_t ri = 0; ri < R && !sh.stop.load(std::memory_order_relaxed); ri++) {
+                const uint64_t kept = cb.kept_in_range(len_of(wi), ri);
+                if (kept == 0) continue;
+                const uint64_t af = (uint64_t)ri * cap;
+                const uint32_t n = (uint32_t)std::min<uint64_t>(cap, A - af);
+                if ((r = scan_load_combinator(w.scan, boff + (wi - b), bbytes, 0, 1, aoff, abytes, A, af, n, cb.side, 8,
+                                              63, w.stream)) < 0)
+                    return r;
+                sync_retired(w, sh);
+                if ((r = scan_run(w.scan, w.stream)) < 0) return r;
+                w.cands += kept;
+                if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
+                if (hits.empty()) continue;
+                report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+                    if (cand >= A) return false;
+                    join(wi, cand, plain);
+                    return true;
+                });
+            }
+        }
+        return 0;
+    }
+    const uint64_t most = std::min<uint64_t>(16ull * cap, UINT32_MAX) / A;  // raw pairs of a fill-mode load; >= 16
+    const size_t words = e - b;
+    for (size_t wb = 0; wb < words && !sh.stop.load(std::memory_order_relaxed);) {
+        uint32_t nw = 0;
+        uint64_t kept = 0;
+        for (; wb + nw < words && nw < most; nw++) {  // one word keeps at most A <= cap pairs: nw >= 1
+            const uint64_t k = cb.kept(len_of(b + wb + nw));
+            if (kept + k > cap) break;
+            kept += k;
+        }
+        if (kept == 0) {
+            wb += nw;
+            continue;
+        }
+        if ((r = scan_load_combinator(w.scan, boff, bbytes, wb, nw, aoff, abytes, A, 0, (uint32_t)A, cb.side, 8, 63,
+                                      w.stream, true)) < 0)
+            return r;
+        uint32_t raw = 0;
+        if ((r = scan_counter_raw(w.scan, w.stream, &raw)) < 0) return r;
+        if (raw != kept) {  // a guard, not the mechanism: the two counts follow from the same lengths
+            fprintf(stderr, "[dwpa] combinator load kept %u pairs where the lengths give %llu\n", raw,
+                    (unsigned long long)kept);
+            return DWPA_E_OVERFLOW;
+        }
+        sync_retired(w, sh);
+        if ((r = scan_run(w.scan, w.stream)) < 0) return r;
+        const size_t first = b + wb;
+        wb += nw;
+        w.cands += kept;
+        if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
+        if (hits.empty()) continue;
+        report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+            const uint64_t word = cand / A - (first - b), ai = cand % A;
+            if (word >= nw) return false;
+            join(first + word, ai, plain);
+            return true;
+        });
+    }
+    return 0;
+}
+
 static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, size_t e, const RuleSet* rules,
-                      const HybridSpec* hy, int slot) {
+                      const HybridSpec* hy, const CombiSpec* cb, int slot) {
     if (e <= b) return 0;
     if (hipSetDevice(w.device) != hipSuccess) return DWPA_E_HIP;
     if (hipStreamWaitEvent(w.stream, w.staged[slot], 0) != hipSuccess) return DWPA_E_HIP;
+    if (cb) return scan_shard_combi(w, sh, c, b, e, *cb, slot);
     const DevBuf& woff = w.off[slot];
     const DevBuf& wbytes = w.bytes[slot];
     const uint32_t cap = scan_batch_cap(w.scan);
@@ -288,7 +472,7 @@ static bool trace_on() {
 
 static int crack_impl(const char* hash_file, const char* const* dicts, size_t ndicts, const char* rules_file, int nec,
                       const char* out_file, const dwpa_config* cfg, int32_t* dict_status,
-                      const HybridSpec* hy = nullptr) {
+                      const HybridSpec* hy = nullptr, CombiSpec* cb = nullptr) {
     const auto t_call = std::chrono::steady_clock::now();
     g_last_stats = dwpa_crack_stats{};  // an early return reports zeros, never the previous call
     g_last_workers.clear();
@@ -314,7 +498,27 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
             fclose(f);
         }
     }
-    if (unreadable || (hy && !hy->valid)) return DWPA_RC_ERROR;
+    if (unreadable || (hy && !hy->valid) || (cb && !cb->valid)) return DWPA_RC_ERROR;
+    if (cb) {  // dicts = {left, right}: the amplifier is read whole, before any device is touched
+        FILE* f = fopen(hash_file, "rb");
+        if (!f) return DWPA_RC_ERROR;
+        fclose(f);
+        const size_t ai = 1 - cb->base_index();
+        const int r = read_amplifier(dicts[ai], cb);
+        if (r == DWPA_E_OVERFLOW) {
+            fprintf(stderr, "[dwpa] list %s: too large to be the amplifier (at most %llu bytes of text and offsets, "
+                            "fewer than 2^32 words); take the other list with amp_side %d (--amplifier %s)\n",
+                    dicts[ai], (unsigned long long)DWPA_COMBI_AMP_MAX_BYTES,
+                    cb->side == DWPA_COMBI_AMP_RIGHT ? DWPA_COMBI_AMP_LEFT : DWPA_COMBI_AMP_RIGHT,
+                    cb->side == DWPA_COMBI_AMP_RIGHT ? "left" : "right");
+            return DWPA_RC_ERROR;
+        }
+        if (r < 0) {
+            if (dict_status) dict_status[ai] = DWPA_E_IO;
+            fprintf(stderr, "[dwpa] dictionary %s: read error\n", dicts[ai]);
+            return DWPA_RC_ERROR;
+        }
+    }
     // the config applies to this call only (dwpa_init's process-wide selection stays as it is)
     if (engine_init() < 0) return DWPA_RC_ERROR;
     std::vector<int> devs = engine_devices(DWPA_CFG_HAS(cfg, device_mask) ? cfg->device_mask : 0);
@@ -376,11 +580,19 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
             if (rc >= 0) rc = scan_create(dev, lp.data(), ll.data(), lines.size(), nec, nc_mode, batch, &w.scan);
             if (rc >= 0 && rp) rc = rules_upload(dev, rules, &w.rules);
             if (rc >= 0 && hy) rc = scan_set_mask(w.scan, *hy->mask);
+            if (rc >= 0 && cb) rc = upload_amplifier(w, *cb);
         }
     const size_t G = work.size();
+    if (rc >= 0 && cb && cb->words() > scan_batch_cap(work[0]->scan)) cb->count_ranges(scan_batch_cap(work[0]->scan));
 
+    // the streamed dictionaries: all of them, or a combinator run's base list (dmap: their places in dicts)
     std::vector<std::string> dpaths;
-    for (size_t i = 0; i < ndicts; i++) dpaths.push_back(dicts[i]);
+    std::vector<size_t> dmap;
+    for (size_t i = 0; i < ndicts; i++)
+        if (!cb || i == cb->base_index()) {
+            dpaths.push_back(dicts[i]);
+            dmap.push_back(i);
+        }
     // Items: the first is 1/16 of a batch of candidates (a device starts after ~1M words have been read, not a
     // whole 16M-word batch: on a dictionary's first pass that read took ~0.5 s of a 21 s C2 pass), doubling to
     // 16 batches (a partial last batch per item then costs ~1 % of its wave rounds).  The reader's chunks start at
@@ -388,7 +600,8 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
     // holding much more than that in memory.
     // A hybrid run divides by its mask's keyspace K: K = 1 sizes items as a plain dictionary run does; K above the
     // batch makes every item one word (first_item = most_item = 1), which is K / batch launches.
-    const size_t nr = hy ? (size_t)hy->mask->keyspace : rp ? rp->size() : 1;
+    // A combinator run divides by its amplifier's word count A in the same way.
+    const size_t nr = cb ? std::max<size_t>(1, (size_t)cb->words()) : hy ? (size_t)hy->mask->keyspace : rp ? rp->size() : 1;
     const size_t first_item = std::max<size_t>(1, batch / nr / 16), most_item = std::max<size_t>(1, 16 * (size_t)batch / nr);
     ChunkSource source(dpaths, first_item * G, 2 * most_item * G);
     // several workers: items of at most 2 batches, so an item handed out just before the readers reach the end
@@ -455,7 +668,7 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
                         it = w.slot_item[slot];
                     }
                     const auto ts = std::chrono::steady_clock::now();
-                    const int r = guarded([&] { return scan_shard(w, sh, *it.chunk, it.b, it.e, rp, hy, slot); });
+                    const int r = guarded([&] { return scan_shard(w, sh, *it.chunk, it.b, it.e, rp, hy, cb, slot); });
                     w.scan_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
                     w.items++;
                     w.words += it.e - it.b;
@@ -483,15 +696,22 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
     source.finish();
     const bool ioerr = items.io_error();
     const std::vector<int> fst = source.file_status();
-    for (size_t i = 0; i < ndicts; i++) {
-        if (fst[i] == ChunkSource::FILE_DAMAGED)
+    for (size_t k = 0; k < dmap.size(); k++) {
+        const size_t i = dmap[k];
+        if (fst[k] == ChunkSource::FILE_DAMAGED)
             fprintf(stderr, "[dwpa] dictionary %s: damaged gzip stream (truncated or corrupt); scanned up to the damage, "
                             "as hashcat's gzread does\n", dicts[i]);
-        else if (fst[i] == ChunkSource::FILE_UNREADABLE)
+        else if (fst[k] == ChunkSource::FILE_UNREADABLE)
             fprintf(stderr, "[dwpa] dictionary %s: read error\n", dicts[i]);
         if (dict_status)
-            dict_status[i] = fst[i] == ChunkSource::FILE_DAMAGED ? DWPA_DICT_DAMAGED
-                             : fst[i] == ChunkSource::FILE_UNREADABLE ? DWPA_E_IO : DWPA_DICT_OK;
+            dict_status[i] = fst[k] == ChunkSource::FILE_DAMAGED ? DWPA_DICT_DAMAGED
+                             : fst[k] == ChunkSource::FILE_UNREADABLE ? DWPA_E_IO : DWPA_DICT_OK;
+    }
+    if (cb && cb->status == DWPA_DICT_DAMAGED) {
+        const size_t ai = 1 - cb->base_index();
+        fprintf(stderr, "[dwpa] dictionary %s: damaged gzip stream (truncated or corrupt); joined up to the damage\n",
+                dicts[ai]);
+        if (dict_status) dict_status[ai] = DWPA_DICT_DAMAGED;
     }
     if (trace_on()) {
         const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -509,6 +729,8 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
             w.bytes[q].release();
             if (w.staged[q]) (void)hipEventDestroy(w.staged[q]);
         }
+        w.amp_off.release();
+        w.amp_bytes.release();
         rules_release(&w.rules);
         if (w.stream) (void)hipStreamDestroy(w.stream);
         if (w.up) (void)hipStreamDestroy(w.up);
@@ -752,6 +974,24 @@ int dwpa_crack_hybrid(const char* hash_file, const char* const* dicts, size_t nd
         }
         return dwpa::crack_impl(hash_file, dicts, ndicts, nullptr, nonce_error_corrections, out_file, cfg, dict_status,
                                 &hy);
+    }, DWPA_RC_ERROR, DWPA_RC_ERROR);
+}
+
+int dwpa_crack_combinator(const char* hash_file, const char* left_dict, const char* right_dict, int amp_side,
+                          int nonce_error_corrections, const char* out_file, const dwpa_config* cfg,
+                          int32_t dict_status[2]) {
+    return dwpa::guarded([&]() -> int {
+        auto cb = std::make_unique<dwpa::CombiSpec>();
+        cb->valid = true;
+        if (amp_side != DWPA_COMBI_AMP_RIGHT && amp_side != DWPA_COMBI_AMP_LEFT) {
+            fprintf(stderr, "[dwpa] amp_side %d: 0 (the right list is the amplifier) or 1 (the left list)\n", amp_side);
+            cb->valid = false;
+        } else {
+            cb->side = amp_side;
+        }
+        const char* const dicts[2] = {left_dict, right_dict};
+        return dwpa::crack_impl(hash_file, dicts, 2, nullptr, nonce_error_corrections, out_file, cfg, dict_status,
+                                nullptr, cb.get());
     }, DWPA_RC_ERROR, DWPA_RC_ERROR);
 }
 

@@ -1637,6 +1637,33 @@ int scan_load_hybrid(dwpa_scan* sc, const uint64_t* off, const uint8_t* bytes, u
     return 0;
 }
 
+// Base words x amplifier words (combi_dev.hip): both lists are the caller's, nothing is kept in the scan.  The counter
+// is zeroed on the stream and counted up by the kernel, as in scan_load_hybrid; fill = true (crack_combinator): up to
+// 16 batches of raw pairs.
+int scan_load_combinator(dwpa_scan* sc, const uint64_t* base_off, const uint8_t* base_bytes, uint64_t first_base,
+                         uint32_t nbase, const uint64_t* amp_off, const uint8_t* amp_bytes, uint64_t amp_words,
+                         uint64_t amp_first, uint32_t amp_count, int amp_side, uint32_t minlen, uint32_t maxlen,
+                         void* stream, bool fill) {
+    if (!sc || (amp_side != DWPA_COMBI_AMP_RIGHT && amp_side != DWPA_COMBI_AMP_LEFT)) return DWPA_E_ARG;
+    const uint64_t most = fill ? std::min<uint64_t>(16 * (uint64_t)sc->batch_cap, UINT32_MAX) : sc->batch_cap;
+    if ((uint64_t)nbase * amp_count > most) return DWPA_E_ARG;
+    // amp_first + amp_count > A, wrap included; A == 0 takes no amp_count but 0
+    if (amp_first > amp_words || amp_count > amp_words - amp_first) return DWPA_E_ARG;
+    uint64_t last_base, last_id;
+    if (__builtin_add_overflow(first_base, (uint64_t)nbase, &last_base) ||
+        __builtin_mul_overflow(last_base, amp_words, &last_id))
+        return DWPA_E_ARG;  // ids are base_index * A + amp_index in 64 bits
+    if (nbase && amp_count && (!base_off || !base_bytes || !amp_off || !amp_bytes)) return DWPA_E_ARG;
+    HIPCHK(hipSetDevice(sc->device));
+    hipStream_t s = as_stream(stream);
+    HIPCHK(hipMemsetAsync(sc->batch.counters.p, 0, 4, s));
+    HIPCHK(launch_prep_combinator(base_off, base_bytes, first_base, nbase, amp_off, amp_bytes, amp_words, amp_first,
+                                  amp_count, amp_side == DWPA_COMBI_AMP_LEFT, minlen, maxlen,
+                                  (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
+                                  (uint32_t*)sc->batch.counters.p, sc->batch_cap, s));
+    return 0;
+}
+
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream) {
     if (!sc || group < 0 || group >= (int)sc->groups.size()) return DWPA_E_ARG;
     HIPCHK(hipSetDevice(sc->device));
@@ -2048,6 +2075,16 @@ int dwpa_scan_load_hybrid(dwpa_scan* scan, const uint64_t* d_offsets, const uint
         if (!scan) RCHK(ensure_init());
         return scan_load_hybrid(scan, d_offsets, d_bytes, first_word, nwords, mask_first, mask_count, mode, minlen,
                                 maxlen, hip_stream);
+    });
+}
+int dwpa_scan_load_combinator(dwpa_scan* scan, const uint64_t* d_base_off, const uint8_t* d_base_bytes,
+                              uint64_t first_base, uint32_t nbase, const uint64_t* d_amp_off,
+                              const uint8_t* d_amp_bytes, uint64_t amp_words, uint64_t amp_first, uint32_t amp_count,
+                              int amp_side, uint32_t minlen, uint32_t maxlen, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!scan) RCHK(ensure_init());
+        return scan_load_combinator(scan, d_base_off, d_base_bytes, first_base, nbase, d_amp_off, d_amp_bytes,
+                                    amp_words, amp_first, amp_count, amp_side, minlen, maxlen, hip_stream);
     });
 }
 int dwpa_scan_pbkdf2(dwpa_scan* scan, int group, void* hip_stream) {

@@ -102,6 +102,12 @@ int scan_load_mask(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream);
 int scan_load_hybrid(dwpa_scan* sc, const uint64_t* off, const uint8_t* bytes, uint64_t first_word, uint32_t nwords,
                      uint64_t mask_first, uint32_t mask_count, int mode, uint32_t minlen, uint32_t maxlen,
                      void* stream, bool fill = false);
+// base words x amplifier words (combi_dev.hip); fill = true (crack_combinator): nbase * amp_count may reach 16
+// batches (below 2^32), as for scan_load_hybrid
+int scan_load_combinator(dwpa_scan* sc, const uint64_t* base_off, const uint8_t* base_bytes, uint64_t first_base,
+                         uint32_t nbase, const uint64_t* amp_off, const uint8_t* amp_bytes, uint64_t amp_words,
+                         uint64_t amp_first, uint32_t amp_count, int amp_side, uint32_t minlen, uint32_t maxlen,
+                         void* stream, bool fill = false);
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream);
 int scan_verify(dwpa_scan* sc, int group, void* stream);
 int scan_run(dwpa_scan* sc, void* stream);

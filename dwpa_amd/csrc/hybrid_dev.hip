@@ -24,27 +24,6 @@
 
 namespace dwpa {
 
-// x moved n bytes (0..63) towards the end of the block, zeros entering at byte 0; bytes pushed past byte 63 are lost.
-// The byte part n & 3 is a funnel shift between neighbouring big-endian words (v_alignbit_b32), the word part n >> 2
-// a 4-stage barrel of conditional moves: every register index is a compile-time constant.
-__device__ __forceinline__ void shift_right_bytes(uint32_t x[16], uint32_t n) {
-    const uint32_t s = n & 3u;
-#pragma unroll
-    for (int j = 15; j >= 0; j--) {
-        const uint32_t hi = j > 0 ? x[j - 1] : 0u;
-        x[j] = __builtin_amdgcn_alignbyte(hi, x[j], s);  // ((hi : x[j]) >> 8s), s = 0: x[j]
-    }
-#pragma unroll
-    for (int step = 8; step >= 1; step >>= 1) {
-        const bool on = ((n >> 2) & (uint32_t)step) != 0;
-#pragma unroll
-        for (int j = 15; j >= 0; j--) {
-            const uint32_t from = j >= step ? x[j - step] : 0u;
-            x[j] = on ? from : x[j];
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void k_prep_hybrid(MaskDigits base, const uint64_t* __restrict__ off,
                                                      const uint8_t* __restrict__ bytes, uint64_t first_word,
                                                      uint32_t total, uint64_t mask_first, uint32_t mask_count,

@@ -32,6 +32,16 @@ hipError_t launch_prep_hybrid(const uint8_t digits[64], const uint64_t* off, con
                               uint32_t npos, bool mask_then_word, uint32_t minlen, uint32_t maxlen,
                               const uint8_t* table, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
                               hipStream_t s);
+// combi_dev.hip: base words [first_base, first_base + nbase) of base_off/base_bytes x amplifier words [amp_first,
+// amp_first + amp_count) of amp_off/amp_bytes, base-major, joined as base || amplifier or (amp_is_left) amplifier ||
+// base -> midstates in compacted slots; kept iff both words <= 63 bytes and minlen <= L + R <= min(maxlen, 64);
+// ids[slot] = base index * amp_words + amplifier index.  The counter (zeroed by the caller) ends as the raw kept
+// count, which may exceed cap.  nbase * amp_count < 2^32.
+hipError_t launch_prep_combinator(const uint64_t* base_off, const uint8_t* base_bytes, uint64_t first_base,
+                                  uint32_t nbase, const uint64_t* amp_off, const uint8_t* amp_bytes, uint64_t amp_words,
+                                  uint64_t amp_first, uint32_t amp_count, bool amp_is_left, uint32_t minlen,
+                                  uint32_t maxlen, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
+                                  hipStream_t s);
 // product launch: issue-pass code object (pbkdf2_module.cpp); DWPA_PBKDF2_PLAIN=1 -> launch_pbkdf2_plain
 // work (nullable): a 4-byte device counter the work-queue kernel may use (zeroed here before the launch)
 hipError_t launch_pbkdf2(const uint32_t* mid, uint32_t cap, uint32_t base, uint32_t count, const uint32_t* counter,

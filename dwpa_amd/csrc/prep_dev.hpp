@@ -1,5 +1,5 @@
 // prep_dev.hpp -- device helpers shared by the candidate-materialisation kernels (kernels.hip, rules_dev.hip,
-// mask_dev.hip, hybrid_dev.hip):
+// mask_dev.hip, hybrid_dev.hip, combi_dev.hip):
 // key bytes -> HMAC-SHA1 key block -> ipad/opad midstates, and wave-aggregated slot compaction.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +31,28 @@ __device__ __forceinline__ void load_key_block(const uint8_t* p, uint32_t len, u
         if (rem <= 0) v = 0;
         else if (rem < 4) v &= 0xffffffffu << (8 * (4 - rem));
         w[j] = v;
+    }
+}
+
+// x moved n bytes (0..63) towards the end of the block, zeros entering at byte 0; bytes pushed past byte 63 are lost.
+// The byte part n & 3 is a funnel shift between neighbouring big-endian words (v_alignbit_b32), the word part n >> 2
+// a 4-stage barrel of conditional moves: every register index is a compile-time constant.  Joins the two halves of
+// a candidate (hybrid_dev.hip, combi_dev.hip).
+__device__ __forceinline__ void shift_right_bytes(uint32_t x[16], uint32_t n) {
+    const uint32_t s = n & 3u;
+#pragma unroll
+    for (int j = 15; j >= 0; j--) {
+        const uint32_t hi = j > 0 ? x[j - 1] : 0u;
+        x[j] = __builtin_amdgcn_alignbyte(hi, x[j], s);  // ((hi : x[j]) >> 8s), s = 0: x[j]
+    }
+#pragma unroll
+    for (int step = 8; step >= 1; step >>= 1) {
+        const bool on = ((n >> 2) & (uint32_t)step) != 0;
+#pragma unroll
+        for (int j = 15; j >= 0; j--) {
+            const uint32_t from = j >= step ? x[j - step] : 0u;
+            x[j] = on ? from : x[j];
+        }
     }
 }
 

@@ -360,6 +360,21 @@ def crack_hybrid(hash_file, dicts, mask, custom=(), mode: int = L.DWPA_HYBRID_WO
     return rc, [int(st[i]) for i in range(len(dl))]
 
 
+def crack_combinator(hash_file, left, right, amp_side: int = L.DWPA_COMBI_AMP_RIGHT,
+                     nonce_error_corrections: int = 8, out_file="help_crack.key", device_mask: int = 0, batch: int = 0,
+                     nc_mode: int = L.DWPA_NC_HASHCAT):
+    """In-process `hashcat -m22000 -a 1 hash_file left right`: every word of `left` followed by every word of `right`
+    (plain or gzip lists), on every selected device.  amp_side names the list held whole in device memory
+    (DWPA_COMBI_AMP_RIGHT, the default, or DWPA_COMBI_AMP_LEFT); the other list is streamed.  Returns (rc,
+    [left_status, right_status]): a hashcat exit code (0 cracked, 1 exhausted, -1 error) and one status per list
+    (DWPA_DICT_OK | DWPA_DICT_DAMAGED | DWPA_E_IO)."""
+    cfg = L.Config(ctypes.sizeof(L.Config), device_mask, batch, nc_mode)
+    st = (ctypes.c_int32 * 2)()
+    rc = L.load().dwpa_crack_combinator(_b(hash_file), _b(left), _b(right), int(amp_side),
+                                        _nc(nonce_error_corrections), _b(out_file), ctypes.byref(cfg), st)
+    return rc, [int(st[0]), int(st[1])]
+
+
 def crack_stats():
     """dwpa_crack_last_stats: {words, candidates, hashes, cracked, seconds, rules, rules_skipped, rules_rejmem} of
     this thread's last crack call."""
@@ -446,6 +461,21 @@ class Scan:
         L.check(self._lib.dwpa_scan_load_hybrid(self._h, d_offsets, d_bytes, _u64(first_word, "first_word"),
                                                 int(nwords), _u64(mask_first, "mask_first"), int(mask_count),
                                                 int(mode), int(minlen), int(maxlen), stream), "scan_load_hybrid")
+
+    def load_combinator(self, base_off: int, base_bytes: int, first_base: int, nbase: int, amp_off: int,
+                        amp_bytes: int, amp_words: int, amp_first: int, amp_count: int,
+                        amp_side: int = L.DWPA_COMBI_AMP_RIGHT, minlen=8, maxlen=63, stream: int = 0):
+        """Base words [first_base, first_base + nbase) of one HBM-resident list x words [amp_first, amp_first +
+        amp_count) of another (the amplifier, amp_words words in all), joined on the GPU as base + amplifier word
+        (DWPA_COMBI_AMP_RIGHT) or amplifier word + base (DWPA_COMBI_AMP_LEFT).  A pair is kept iff both words are at most
+        63 bytes and the joined length is in minlen..maxlen; candidate id = base index * amp_words + amplifier index."""
+        for v, what in ((nbase, "nbase"), (amp_count, "amp_count"), (minlen, "minlen"), (maxlen, "maxlen")):
+            if not 0 <= int(v) < 2**32:
+                raise L.DwpaError(L.DWPA_E_ARG, f"{what} {v} is outside uint32")
+        L.check(self._lib.dwpa_scan_load_combinator(self._h, base_off, base_bytes, _u64(first_base, "first_base"),
+                                                    int(nbase), amp_off, amp_bytes, _u64(amp_words, "amp_words"),
+                                                    _u64(amp_first, "amp_first"), int(amp_count), int(amp_side),
+                                                    int(minlen), int(maxlen), stream), "scan_load_combinator")
 
     def pbkdf2(self, group: int = 0, stream: int = 0):
         L.check(self._lib.dwpa_scan_pbkdf2(self._h, group, stream), "scan_pbkdf2")

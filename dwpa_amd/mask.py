@@ -1,6 +1,6 @@
-"""``python -m dwpa_amd.mask HASHFILE MASK`` -- hashcat's ``-m 22000 -a 3`` mask attack on libdwpa22000.so, and its
+"""``python -m dwpa_amd.mask HASHFILE MASK`` -- hashcat's ``-m 22000 -a 3`` mask attack on libdwpa22000.so, its
 hybrid attacks ``-a 6 HASHFILE DICT [DICT...] MASK`` (word + mask) and ``-a 7 HASHFILE MASK DICT [DICT...]`` (mask +
-word).
+word), and its combinator attack ``-a 1 HASHFILE LEFT RIGHT`` (word of one list + word of another).
 
 It takes hashcat's spellings: ``-1``..``-4`` custom sets, ``-s/--skip``, ``-l/--limit``, ``-i --increment-min
 --increment-max``, ``-d`` (devices, numbered from 1), ``-o``, ``--nonce-error-corrections``.  The exit status is the
@@ -10,6 +10,12 @@ file and stay on the host.
 With ``-a 6`` / ``-a 7`` the dictionaries are plain or gzip wordlists (``$HEX[]`` words decoded); ``--stdout`` then
 takes no hash file (``-a 6 --stdout DICT... MASK``) and prints every word x mask candidate, unfiltered, word-major
 with the mask index fastest.  ``-s``, ``-l``, ``-i`` and ``--keyspace`` belong to ``-a 3`` only.
+
+With ``-a 1`` every candidate is a word of LEFT followed by a word of RIGHT.  ``--amplifier right`` (the default)
+holds RIGHT whole in device memory and streams LEFT; ``--amplifier left`` holds LEFT and streams RIGHT, for a RIGHT
+too big to hold.  The candidates are the same, their order differs: the streamed list's words are the outer loop.
+``-a 1 --stdout LEFT RIGHT`` takes no hash file and prints every pair, unfiltered, in that order.  ``-s``, ``-l``,
+``-i``, ``--keyspace``, ``-1``..``-4`` and hashcat's single rules ``-j`` / ``-k`` are not available with ``-a 1``.
 
 The candidates of a mask are hashcat's; their ORDER is the library's own (last position fastest, Python's
 ``itertools.product`` order), so ``-s`` / ``-l`` windows do not name the candidates hashcat's windows name.
@@ -33,7 +39,11 @@ def _parser() -> argparse.ArgumentParser:
                         "the mask alone with --keyspace / --stdout")
     p.add_argument("-a", "--attack-mode", type=int, default=3, metavar="N",
                    help="3 mask (default); 6 wordlist + mask: HASHFILE DICT [DICT...] MASK; 7 mask + wordlist: "
-                        "HASHFILE MASK DICT [DICT...]")
+                        "HASHFILE MASK DICT [DICT...]; 1 combinator: HASHFILE LEFT RIGHT")
+    p.add_argument("--amplifier", default="right", metavar="SIDE",
+                   help="-a 1: the list held whole in device memory, right (default) or left; the other is streamed")
+    p.add_argument("-j", "--rule-left", default=None, metavar="RULE", help="hashcat's -a 1 single rule: not supported")
+    p.add_argument("-k", "--rule-right", default=None, metavar="RULE", help="hashcat's -a 1 single rule: not supported")
     for k in "1234":
         p.add_argument("-" + k, "--custom-charset" + k, dest="c" + k, metavar="CS", help="custom set ?" + k)
     p.add_argument("--hex-charset", action="store_true", help="the custom sets are given in hex")
@@ -67,10 +77,14 @@ def main(argv=None) -> int:
         a = p.parse_args(argv)
     except SystemExit as e:  # argparse: 0 after --help, 2 for bad arguments
         return 0 if e.code in (0, None) else 255
+    if a.rule_left is not None or a.rule_right is not None:
+        return _fail("the single rules -j / -k are not supported")
+    if a.attack_mode == 1:
+        return _combinator(a)
     if a.attack_mode in (6, 7):
         return _hybrid(a)
     if a.attack_mode != 3:
-        return _fail("-a takes 3 (mask), 6 (wordlist + mask) or 7 (mask + wordlist)")
+        return _fail("-a takes 1 (combinator), 3 (mask), 6 (wordlist + mask) or 7 (mask + wordlist)")
     host_only = a.keyspace or a.stdout
     if not (len(a.args) == 2 or (host_only and len(a.args) == 1)):
         return _fail("expected HASHFILE MASK" + (" or MASK" if host_only else ""))
@@ -219,6 +233,51 @@ def _hybrid(a) -> int:
                st["seconds"]), file=sys.stderr)
         return rc
     return _fail("crack_hybrid failed")
+
+
+def _combinator(a) -> int:
+    """-a 1: HASHFILE LEFT RIGHT as hashcat's; --stdout takes the two lists alone."""
+    if a.skip or a.limit or a.increment or a.increment_min or a.increment_max or a.keyspace:
+        return _fail("-s, -l, -i and --keyspace are not available with -a 1")
+    if any(getattr(a, "c" + k) is not None for k in "1234") or a.hex_charset:
+        return _fail("-1..-4 belong to a mask: not available with -a 1")
+    if a.amplifier not in ("right", "left"):
+        return _fail("--amplifier takes right or left")
+    side = L.DWPA_COMBI_AMP_RIGHT if a.amplifier == "right" else L.DWPA_COMBI_AMP_LEFT
+    ops = a.args if a.stdout else a.args[1:]
+    if len(ops) != 2 or (not a.stdout and len(a.args) != 3):
+        return _fail("expected " + ("" if a.stdout else "HASHFILE ") + "LEFT RIGHT")
+    left, right = ops
+    try:
+        for d in ops:
+            if not os.path.isfile(d) or not os.access(d, os.R_OK):
+                return _fail(f"dictionary {d}: cannot be opened")
+        if a.stdout:
+            out = sys.stdout.buffer
+            if side == L.DWPA_COMBI_AMP_RIGHT:
+                amp = list(_words(right))
+                for w in _words(left):
+                    out.write(b"".join(w + r + b"\n" for r in amp))
+            else:
+                amp = list(_words(left))
+                for w in _words(right):
+                    out.write(b"".join(l + w + b"\n" for l in amp))
+            out.flush()
+            return 0
+        devices = _devices(a)
+        if devices < 0:
+            return 255
+        rc, status = M.crack_combinator(a.args[0], left, right, side, a.nonce_error_corrections, a.outfile,
+                                        device_mask=devices, batch=a.batch)
+    except (L.DwpaError, OSError) as e:
+        return _fail(str(e))
+    if rc in (0, 1):
+        st = M.crack_stats()
+        print("dwpa_amd.mask: %s, %d/%d hashlines cracked, %d words, %d candidates in %.1f s" %
+              ("cracked" if rc == 0 else "exhausted", st["cracked"], st["hashes"], st["words"], st["candidates"],
+               st["seconds"]), file=sys.stderr)
+        return rc
+    return _fail("crack_combinator failed")
 
 
 def _prefix(mask: bytes, n: int) -> bytes:

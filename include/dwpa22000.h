@@ -43,7 +43,8 @@ extern "C" {
                                 Added since without a new version or error code, discoverable by symbol: the mask
                                 attack -- dwpa_mask_keyspace, dwpa_mask_candidate, dwpa_scan_set_mask,
                                 dwpa_scan_load_mask, dwpa_crack_mask; the hybrid attacks -- dwpa_scan_load_hybrid,
-                                dwpa_crack_hybrid */
+                                dwpa_crack_hybrid; the combinator attack -- dwpa_scan_load_combinator,
+                                dwpa_crack_combinator */
 
 /* ---- return codes ------------------------------------------------------------------------------------------ */
 #define DWPA_MISS 0            /* no key matched (PHP: False)                                                 */
@@ -354,6 +355,43 @@ int dwpa_crack_hybrid(const char *hash_file, const char *const *dicts, size_t nd
                       const dwpa_bytes custom[4], int mode, int nonce_error_corrections, const char *out_file,
                       const dwpa_config *cfg, int32_t *dict_status /* nullable */);
 
+/* ---- combinator attack: hashcat -a 1 (word of one list || word of another) -------------------------------------
+ * Candidate: left || right, left a word of the first list and right a word of the second, as `hashcat -a 1 left
+ * right` joins them.
+ * Amplifier and base -- the amplifier list is held whole in device memory, the base list is streamed through the
+ * dictionary feed.  DWPA_COMBI_AMP_RIGHT (the default): the right list is the amplifier.  DWPA_COMBI_AMP_LEFT: the left
+ * list is the amplifier, for a right list too big to hold.  The side changes which list is resident and the order of
+ * the candidates, never the join: it is always left || right.
+ * Order and id -- base-major, amplifier index fastest: id = base_index * A + amp_index.  A is the amplifier's word
+ * count as read: every line counts, empty and overlong ones included, so an index names a line.  Parity with
+ * hashcat's order is unpinned, as for -a 3 / 6 / 7; the candidate set is the same.
+ * Filter: a pair is kept iff both words are <= 63 bytes and minlen <= L + R <= maxlen (the crack call uses 8..63; a
+ * scan load treats maxlen above 64 as 64, one HMAC key block).  The decision is per pair.  An empty word is an
+ * ordinary word.  Dropped pairs leave no slots.  Two different pairs can be the same string (a || bc, ab || c): both
+ * are candidates with their own ids, and the crack call reports a line once, lowest id first. */
+#define DWPA_COMBI_AMP_RIGHT 0
+#define DWPA_COMBI_AMP_LEFT  1
+/* The amplifier list of dwpa_crack_combinator: fewer than 2^32 words, and decoded text plus 8-byte offsets of at most
+ * this many bytes (it is held once on the host and once per worker on its device). */
+#define DWPA_COMBI_AMP_MAX_BYTES (1ull << 30)
+/* hashcat -m 22000 -a 1 hash_file left_dict right_dict -o out_file, with everything dwpa_crack_hybrid does, the
+ * amplifier list standing where the mask does: hash file, outfile records (the PSK rebuilt on the host from the two
+ * words), return codes, nonce_error_corrections, cfg, plain or gzip lists with $HEX[] words and CRLF, every selected
+ * device with DWPA_CRACK_SHARDS_PER_DEVICE workers each, cross-worker retirement, stop when every line is cracked.
+ * The amplifier list (amp_side: DWPA_COMBI_AMP_RIGHT or DWPA_COMBI_AMP_LEFT) is read whole into host memory once and
+ * uploaded once per worker; the base list is streamed.  Loads are sized from the two lists' lengths, not by trial:
+ * A <= batch: a launch holds whole base words x the whole amplifier, as many as fill the batch exactly; A > batch: one
+ * base word x consecutive amplifier ranges of `batch` (a range that keeps no pair costs no launch).
+ * DWPA_RC_ERROR before any device is touched: an unknown amp_side, a missing hash file, an unreadable list (its
+ * dict_status entry is DWPA_E_IO, whatever else is wrong with the call), an amplifier list above the limit
+ * (DWPA_COMBI_AMP_MAX_BYTES or 2^32 - 1 words: the message names the other amp_side).
+ * dict_status (nullable): [0] the left list, [1] the right list.
+ * dwpa_crack_last_stats afterwards: words = base words read, candidates = kept pairs derived (for an exhausted run the
+ * exact count that follows from the two lists' lengths); dwpa_crack_worker_stats as for dwpa_crack_files. */
+int dwpa_crack_combinator(const char *hash_file, const char *left_dict, const char *right_dict, int amp_side,
+                          int nonce_error_corrections, const char *out_file, const dwpa_config *cfg,
+                          int32_t dict_status[2] /* nullable: left, right */);
+
 /* hashcat rules (the whole rule language of hashcat >= 6.2.6: every mangling, reject and memory function; one
  * rule per line, '#' comments; semantics in dwpa_amd/csrc/rules.hpp and oracle/rules.py).  The text entry points
  * below (dwpa_rules_expand, dwpa_rules_apply_host, dwpa_rules_count, dwpa_scan_set_rules) are the interpreter and
@@ -436,6 +474,21 @@ int dwpa_scan_load_mask(dwpa_scan *scan, uint64_t first, uint32_t count, void *h
 int dwpa_scan_load_hybrid(dwpa_scan *scan, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t first_word,
                           uint32_t nwords, uint64_t mask_first, uint32_t mask_count, int mode, uint32_t minlen,
                           uint32_t maxlen, void *hip_stream);
+/* Combinator candidates ("combinator attack" above) of base words [first_base, first_base + nbase) of one
+ * HBM-resident list (d_base_off: at least first_base + nbase + 1 offsets) x the words [amp_first, amp_first +
+ * amp_count) of another (d_amp_off: at least amp_first + amp_count + 1 offsets; amp_words = A, the word count its ids
+ * are formed with), base-major: nbase * amp_count raw pairs, the kept ones compacted into slots in that order,
+ * ids[slot] = base_index * A + amp_index, dwpa_scan_loaded = the kept count.  amp_side says which list stands left:
+ * DWPA_COMBI_AMP_RIGHT joins base || amplifier, DWPA_COMBI_AMP_LEFT amplifier || base.  The call is stateless (both
+ * lists are passed each time) and does not synchronise with the host.  A byte buffer needs no padding: only dwords
+ * that hold a byte of a kept word are read.  nbase == 0 or amp_count == 0 loads nothing.  DWPA_E_ARG (the scan stays
+ * usable): amp_side not 0 or 1, nbase * amp_count > batch, amp_first + amp_count > A (wrap included; so A == 0 with
+ * amp_count > 0), (first_base + nbase) * A beyond 64 bits (wrap of the sum included).  Without a device:
+ * DWPA_E_NODEV. */
+int dwpa_scan_load_combinator(dwpa_scan *scan, const uint64_t *d_base_off, const uint8_t *d_base_bytes,
+                              uint64_t first_base, uint32_t nbase, const uint64_t *d_amp_off,
+                              const uint8_t *d_amp_bytes, uint64_t amp_words /* A */, uint64_t amp_first,
+                              uint32_t amp_count, int amp_side, uint32_t minlen, uint32_t maxlen, void *hip_stream);
 /* Stages 2 and 3 for ESSID group g (PMKs of the loaded batch, then every uncracked line of that ESSID). */
 int dwpa_scan_pbkdf2(dwpa_scan *scan, int group, void *hip_stream);
 int dwpa_scan_verify(dwpa_scan *scan, int group, void *hip_stream);
