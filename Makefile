@@ -9,7 +9,7 @@ HDRS := $(wildcard $(SRC)/*.hpp) include/dwpa22000.h
 OBJS := $(OBJ)/kernels.o $(OBJ)/rules_dev.o $(OBJ)/engine.o $(OBJ)/m22000_host.o $(OBJ)/crack.o $(OBJ)/rules.o \
         $(OBJ)/pbkdf2_module.o $(OBJ)/pbkdf2_hsaco.o $(OBJ)/host_crypto.o $(OBJ)/host_check.o \
         $(OBJ)/mask.o $(OBJ)/mask_dev.o $(OBJ)/crack_mask.o $(OBJ)/hybrid_dev.o \
-        $(OBJ)/combi_dev.o
+        $(OBJ)/combi_dev.o $(OBJ)/chain.o $(OBJ)/chain_dev.o $(OBJ)/crack_chain.o
 LLVM := /opt/rocm/lib/llvm/bin
 ISSUE_RULE ?= sched=1:alt:orig:asmnop,before_half
 
@@ -57,12 +57,13 @@ $(LIB): $(OBJS)
 oracle:
 	$(MAKE) -s -C oracle
 
-asm: $(SRC)/kernels.hip $(SRC)/mask_dev.hip $(SRC)/hybrid_dev.hip $(SRC)/combi_dev.hip $(HDRS)
+asm: $(SRC)/kernels.hip $(SRC)/mask_dev.hip $(SRC)/hybrid_dev.hip $(SRC)/combi_dev.hip $(SRC)/chain_dev.hip $(HDRS)
 	@mkdir -p build/asm
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $< -o build/asm/kernels.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/mask_dev.hip -o build/asm/mask_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/hybrid_dev.hip -o build/asm/hybrid_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/combi_dev.hip -o build/asm/combi_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/chain_dev.hip -o build/asm/chain_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 
 clean:
 	rm -rf build $(LIB)
@@ -73,7 +74,7 @@ clean:
 tools: tools/bin/valu_peak tools/bin/pbkdf2_lab tools/bin/valu_lat tools/bin/valu_peak64 tools/bin/inflate_bench \
        tools/bin/inflate_check tools/bin/item_queue_check tools/bin/rules_fuzz_asan tools/bin/clock_idle \
        tools/bin/inflate_check_tsan tools/bin/tail_placement tools/bin/parse_fuzz_asan tools/bin/host_check_fuzz_asan tools/bin/host_pbkdf2_paths tools/bin/vgpr_bank \
-       tools/bin/mask_fuzz_asan
+       tools/bin/mask_fuzz_asan tools/bin/chain_fuzz_asan
 
 tools/bin/valu_lat: tools/valu_lat.hip
 	@mkdir -p tools/bin
@@ -118,6 +119,12 @@ tools/bin/mask_fuzz_asan: tools/mask_fuzz.cpp $(SRC)/mask.cpp $(SRC)/mask.hpp in
 	@mkdir -p tools/bin
 	$(HIPCC) -O1 -g -std=c++17 -Iinclude -I$(SRC) -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
 	    -o $@ tools/mask_fuzz.cpp $(SRC)/mask.cpp
+
+# host fuzz of the chain attack's keyspace / split arithmetic under AddressSanitizer + UBSan: chain.cpp alone
+tools/bin/chain_fuzz_asan: tools/chain_fuzz.cpp $(SRC)/chain.cpp $(SRC)/chain.hpp include/dwpa22000.h
+	@mkdir -p tools/bin
+	$(HIPCC) -O1 -g -std=c++17 -Iinclude -I$(SRC) -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	    -o $@ tools/chain_fuzz.cpp $(SRC)/chain.cpp
 
 tools/bin/parse_fuzz_asan: tools/parse_fuzz.cpp $(SRC)/m22000_host.cpp $(SRC)/m22000_host.hpp $(SRC)/tables.hpp
 	@mkdir -p tools/bin

@@ -13,12 +13,15 @@ this package is its Python host side:
   (``python -m dwpa_amd.mask -a 6|7``); :meth:`Scan.load_hybrid` is their scan-path load
 * :func:`crack_combinator` -- hashcat ``-a 1`` combinator attack, word of one list + word of another
   (``python -m dwpa_amd.mask -a 1``); :meth:`Scan.load_combinator` is its scan-path load
+* :func:`crack_chain`      -- chain attack, up to four word lists and masks joined left to right
+  (``python -m dwpa_amd.chain``); :meth:`Scan.set_chain` / :meth:`Scan.load_chain` are its scan-path calls,
+  :func:`chain_keyspace` / :func:`chain_split` / :func:`chain_candidate` its host-only helpers
 * :mod:`dwpa_amd.help_crack` -- ``run_cracker`` replacement for help_crack.py
 """
-from ._lib import (DWPA_COMBI_AMP_LEFT, DWPA_COMBI_AMP_RIGHT, DWPA_HYBRID_MASK_WORD,  # noqa: F401
-                   DWPA_HYBRID_WORD_MASK, DwpaError, load)
-from .m22000 import (BatchJobs, check_batch, check_key_m22000, crack_combinator, crack_files,  # noqa: F401
-                     crack_hybrid, crack_mask,
+from ._lib import (DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS, DWPA_COMBI_AMP_LEFT,  # noqa: F401
+                   DWPA_COMBI_AMP_RIGHT, DWPA_HYBRID_MASK_WORD, DWPA_HYBRID_WORD_MASK, DwpaError, load)
+from .m22000 import (BatchJobs, chain_candidate, chain_keyspace, chain_split, check_batch,  # noqa: F401
+                     check_key_m22000, crack_chain, crack_combinator, crack_files, crack_hybrid, crack_mask,
                      device_count, group_by_essid, mask_candidate, mask_keyspace, check_stats, hash_m22000, hc_unhex, init,
                      parse_m22000, pbkdf2_pmk, rules_count, rules_count_ex, rules_expand, Scan)
 
@@ -26,4 +29,6 @@ __all__ = ["DwpaError", "load", "BatchJobs", "check_key_m22000", "check_batch", 
            "crack_files", "rules_count", "rules_count_ex", "check_stats", "rules_expand", "device_count", "Scan",
            "parse_m22000", "group_by_essid", "init", "crack_mask", "mask_keyspace", "mask_candidate",
            "crack_hybrid", "DWPA_HYBRID_WORD_MASK", "DWPA_HYBRID_MASK_WORD",
-           "crack_combinator", "DWPA_COMBI_AMP_RIGHT", "DWPA_COMBI_AMP_LEFT"]
+           "crack_combinator", "DWPA_COMBI_AMP_RIGHT", "DWPA_COMBI_AMP_LEFT",
+           "crack_chain", "chain_keyspace", "chain_split", "chain_candidate", "DWPA_CHAIN_LIST", "DWPA_CHAIN_MASK",
+           "DWPA_CHAIN_MAX_PARTS"]

@@ -22,6 +22,7 @@ DWPA_NC_PHP, DWPA_NC_HASHCAT = 0, 1
 DWPA_NC_MAX = 65664  # the largest nc / nonce_error_corrections taken (include/dwpa22000.h)
 DWPA_HYBRID_WORD_MASK, DWPA_HYBRID_MASK_WORD = 6, 7  # hashcat -a 6 (word || mask) / -a 7 (mask || word)
 DWPA_COMBI_AMP_RIGHT, DWPA_COMBI_AMP_LEFT = 0, 1  # hashcat -a 1: the list held whole in device memory
+DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS = 0, 1, 4  # chain attack: the kind of a part, the most parts
 DWPA_DICT_OK, DWPA_DICT_DAMAGED = 0, 1  # dwpa_crack_files_ex per-dictionary status (or DWPA_E_IO)
 DWPA_RULES_DEFAULT, DWPA_RULES_HASHCAT, DWPA_RULES_FULL = 0, 1, 2  # dwpa_config.rule_mode
 DWPA_BACKEND_DEVICE, DWPA_BACKEND_HOST_SMALL, DWPA_BACKEND_HOST_FALLBACK = 0, 1, 2  # dwpa_check_stats.backend
@@ -94,6 +95,15 @@ class Hit(ctypes.Structure):
                 ("nc_valid", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 2), ("pmk", ctypes.c_uint8 * 32)]
 
 
+class ChainPart(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("d_offsets", ctypes.c_void_p), ("d_bytes", ctypes.c_void_p),
+                ("nwords", ctypes.c_uint64), ("mask", ctypes.c_char_p), ("mask_len", ctypes.c_size_t)]
+
+
+class ChainSpec(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("text", ctypes.c_char_p)]
+
+
 _P = ctypes.c_void_p
 SIGNATURES = {
     "dwpa_abi_version": ([], ctypes.c_int),
@@ -155,6 +165,16 @@ SIGNATURES = {
                                   ctypes.c_int),
     "dwpa_crack_combinator": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
                                ctypes.c_char_p, ctypes.POINTER(Config), ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "dwpa_scan_set_chain": ([_P, ctypes.POINTER(ChainPart), ctypes.c_uint32, ctypes.POINTER(Bytes),
+                             ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_scan_load_chain": ([_P, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _P], ctypes.c_int),
+    "dwpa_chain_keyspace": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)],
+                            ctypes.c_int),
+    "dwpa_chain_split": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32, ctypes.c_uint64,
+                          ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_crack_chain": ([ctypes.c_char_p, ctypes.POINTER(ChainSpec), ctypes.c_uint32, ctypes.POINTER(Bytes),
+                          ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config),
+                          ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "dwpa_crack_mask": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Bytes), ctypes.c_uint64, ctypes.c_uint64,
                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)],
                         ctypes.c_int),

@@ -34,6 +34,7 @@
 #include "kernels.hpp"
 #include "m22000_host.hpp"
 #include "mask.hpp"
+#include "chain.hpp"
 
 namespace dwpa {
 
@@ -1478,6 +1479,21 @@ struct dwpa_scan {
     bool mask_set = false;
     dwpa::Mask mask;
     dwpa::DevBuf mask_tab;
+    // dwpa_scan_set_chain: the parts as given (the lists' device pointers are the caller's), the parsed mask of every
+    // mask part (host copy: dwpa_scan_load_chain decomposes `first` with it) and one device table each; mask_tab is not
+    // touched
+    struct ChainPart {
+        bool is_mask = false;
+        const uint64_t* off = nullptr;
+        const uint8_t* bytes = nullptr;
+        uint64_t radix = 0;
+        std::unique_ptr<dwpa::Mask> mask;
+        dwpa::DevBuf tab;
+    };
+    bool chain_set = false;
+    uint32_t chain_nparts = 0;
+    uint64_t chain_keyspace = 0;
+    ChainPart chain[DWPA_CHAIN_MAX_PARTS];
 };
 
 namespace dwpa {
@@ -1547,6 +1563,7 @@ void scan_destroy(dwpa_scan* sc) {
     sc->lines.release(); sc->atts.release(); sc->pool.release(); sc->salt.release(); sc->segs.release();
     sc->mg_pmk.release(); sc->mg_gsalt.release(); sc->mg_list.release(); sc->mg_poff.release();
     sc->mask_tab.release();
+    for (auto& cp : sc->chain) cp.tab.release();
     sc->batch.mid.release(); sc->batch.pmk.release(); sc->batch.ids.release(); sc->batch.hits.release();
     sc->batch.counters.release();
     delete sc;
@@ -1661,6 +1678,84 @@ int scan_load_combinator(dwpa_scan* sc, const uint64_t* base_off, const uint8_t*
                                   amp_count, amp_side == DWPA_COMBI_AMP_LEFT, minlen, maxlen,
                                   (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
                                   (uint32_t*)sc->batch.counters.p, sc->batch_cap, s));
+    return 0;
+}
+
+// A chain of 1..4 parts (chain_dev.hip).  Everything is parsed and checked before the scan changes, so a refused call
+// leaves the previous chain set; a new chain replaces it after the launches that still read the old tables are done.
+int scan_set_chain(dwpa_scan* sc, const dwpa_chain_part* parts, uint32_t nparts, const dwpa_bytes* custom,
+                   uint64_t* keyspace) {
+    if (!sc || !parts || nparts == 0 || nparts > CHAIN_MAX_PARTS) return DWPA_E_ARG;
+    std::unique_ptr<Mask> masks[CHAIN_MAX_PARTS];
+    uint64_t radix[CHAIN_MAX_PARTS];
+    for (uint32_t p = 0; p < nparts; p++) {
+        if (parts[p].kind == DWPA_CHAIN_MASK) {
+            masks[p] = std::make_unique<Mask>();
+            RCHK(mask_parse(parts[p].mask, parts[p].mask_len, custom, masks[p].get()));
+            radix[p] = masks[p]->keyspace;
+        } else if (parts[p].kind == DWPA_CHAIN_LIST) {
+            if (parts[p].nwords > UINT32_MAX || !parts[p].d_offsets) return DWPA_E_ARG;
+            radix[p] = parts[p].nwords;
+        } else {
+            return DWPA_E_ARG;
+        }
+    }
+    uint64_t K;
+    RCHK(chain_keyspace(radix, nparts, &K));
+    HIPCHK(hipSetDevice(sc->device));
+    HIPCHK(hipDeviceSynchronize());
+    sc->chain_set = false;
+    std::vector<uint8_t> tab(MASK_TABLE_BYTES);
+    for (uint32_t p = 0; p < nparts; p++) {
+        dwpa_scan::ChainPart& cp = sc->chain[p];
+        cp.is_mask = masks[p] != nullptr;
+        cp.off = parts[p].d_offsets;
+        cp.bytes = parts[p].d_bytes;
+        cp.radix = radix[p];
+        if (cp.is_mask) {
+            mask_table(*masks[p], tab.data());
+            RCHK(cp.tab.ensure(MASK_TABLE_BYTES));
+            HIPCHK(hipMemcpy(cp.tab.p, tab.data(), MASK_TABLE_BYTES, hipMemcpyHostToDevice));
+        }
+        cp.mask = std::move(masks[p]);
+    }
+    sc->chain_nparts = nparts;
+    sc->chain_keyspace = K;
+    sc->chain_set = true;
+    if (keyspace) *keyspace = K;
+    return 0;
+}
+
+// No host synchronisation: the digits of `first` travel in the kernel arguments; the counter is zeroed on the stream
+// and counted up by the kernel, as in scan_load_hybrid.
+int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen, void* stream) {
+    if (!sc || !sc->chain_set || count > sc->batch_cap) return DWPA_E_ARG;
+    const uint64_t K = sc->chain_keyspace;
+    if (first > K || count > K - first) return DWPA_E_ARG;  // first + count > K, also when the sum wraps
+    HIPCHK(hipSetDevice(sc->device));
+    hipStream_t s = as_stream(stream);
+    HIPCHK(hipMemsetAsync(sc->batch.counters.p, 0, 4, s));
+    if (count == 0) return 0;  // first == K, or K == 0, only with count 0: nothing is generated
+    ChainPartLaunch lp[CHAIN_MAX_PARTS];
+    uint64_t radix[CHAIN_MAX_PARTS], digit[CHAIN_MAX_PARTS];
+    for (uint32_t p = 0; p < sc->chain_nparts; p++) radix[p] = sc->chain[p].radix;
+    RCHK(chain_split(radix, sc->chain_nparts, first, digit));
+    for (uint32_t p = 0; p < sc->chain_nparts; p++) {
+        const dwpa_scan::ChainPart& cp = sc->chain[p];
+        lp[p].is_mask = cp.is_mask;
+        lp[p].radix = cp.radix;
+        lp[p].digit = digit[p];
+        if (cp.is_mask) {
+            lp[p].table = (const uint8_t*)cp.tab.p;
+            lp[p].npos = cp.mask->npos;
+            mask_digits(*cp.mask, digit[p], lp[p].digits);
+        } else {
+            lp[p].off = cp.off;
+            lp[p].bytes = cp.bytes;
+        }
+    }
+    HIPCHK(launch_prep_chain(lp, sc->chain_nparts, first, count, minlen, maxlen, (uint32_t*)sc->batch.mid.p,
+                             (uint64_t*)sc->batch.ids.p, (uint32_t*)sc->batch.counters.p, sc->batch_cap, s));
     return 0;
 }
 
@@ -2085,6 +2180,23 @@ int dwpa_scan_load_combinator(dwpa_scan* scan, const uint64_t* d_base_off, const
         if (!scan) RCHK(ensure_init());
         return scan_load_combinator(scan, d_base_off, d_base_bytes, first_base, nbase, d_amp_off, d_amp_bytes,
                                     amp_words, amp_first, amp_count, amp_side, minlen, maxlen, hip_stream);
+    });
+}
+int dwpa_scan_set_chain(dwpa_scan* scan, const dwpa_chain_part* parts, uint32_t nparts, const dwpa_bytes custom[4],
+                        uint64_t* keyspace) {
+    return guarded([&]() -> int {
+        if (!scan) {  // no scan can exist without a device: say so first
+            RCHK(ensure_init());
+            return DWPA_E_ARG;
+        }
+        return scan_set_chain(scan, parts, nparts, custom, keyspace);
+    });
+}
+int dwpa_scan_load_chain(dwpa_scan* scan, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen,
+                         void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!scan) RCHK(ensure_init());
+        return scan_load_chain(scan, first, count, minlen, maxlen, hip_stream);
     });
 }
 int dwpa_scan_pbkdf2(dwpa_scan* scan, int group, void* hip_stream) {

@@ -1,4 +1,5 @@
-// engine.hpp -- internal interfaces of libdwpa22000.so shared by engine.cpp and crack.cpp.
+// engine.hpp -- internal interfaces of libdwpa22000.so shared by engine.cpp, crack.cpp, crack_mask.cpp and
+// crack_chain.cpp.
 #pragma once
 #include <stdint.h>
 
@@ -108,6 +109,10 @@ int scan_load_combinator(dwpa_scan* sc, const uint64_t* base_off, const uint8_t*
                          uint32_t nbase, const uint64_t* amp_off, const uint8_t* amp_bytes, uint64_t amp_words,
                          uint64_t amp_first, uint32_t amp_count, int amp_side, uint32_t minlen, uint32_t maxlen,
                          void* stream, bool fill = false);
+// a chain of 1..4 lists and masks (chain_dev.hip); the lists' device pointers stay the caller's
+int scan_set_chain(dwpa_scan* sc, const dwpa_chain_part* parts, uint32_t nparts, const dwpa_bytes* custom,
+                   uint64_t* keyspace);
+int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen, void* stream);
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream);
 int scan_verify(dwpa_scan* sc, int group, void* stream);
 int scan_run(dwpa_scan* sc, void* stream);

@@ -42,6 +42,24 @@ hipError_t launch_prep_combinator(const uint64_t* base_off, const uint8_t* base_
                                   uint64_t amp_first, uint32_t amp_count, bool amp_is_left, uint32_t minlen,
                                   uint32_t maxlen, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
                                   hipStream_t s);
+// chain_dev.hip: raw candidates [first, first + count) of a chain of 1..4 parts (lists in HBM and masks, chain.hpp),
+// joined left to right -> midstates in compacted slots; kept iff every list word <= 63 bytes and minlen <= total
+// length <= min(maxlen, 64); ids[slot] = the raw index.  The counter (zeroed by the caller) ends as the kept count.
+// The caller has checked first + count <= K and count <= cap, and decomposed `first`: part p's digit (a list's word
+// index, or a mask part's own index as its 64 position digits).
+struct ChainPartLaunch {
+    bool is_mask = false;
+    const uint64_t* off = nullptr;   // list: radix + 1 byte offsets into bytes
+    const uint8_t* bytes = nullptr;
+    const uint8_t* table = nullptr;  // mask: the device copy of mask_table (mask.hpp)
+    uint32_t npos = 0;               // mask: positions
+    uint64_t radix = 0;              // a list's word count (< 2^32), a mask's keyspace
+    uint64_t digit = 0;              // digit of `first` at this part, < radix
+    uint8_t digits[64] = {};         // mask: mask_digits of `digit`
+};
+hipError_t launch_prep_chain(const ChainPartLaunch* parts, uint32_t nparts, uint64_t first, uint32_t count,
+                             uint32_t minlen, uint32_t maxlen, uint32_t* mid, uint64_t* ids, uint32_t* counter,
+                             uint32_t cap, hipStream_t s);
 // product launch: issue-pass code object (pbkdf2_module.cpp); DWPA_PBKDF2_PLAIN=1 -> launch_pbkdf2_plain
 // work (nullable): a 4-byte device counter the work-queue kernel may use (zeroed here before the launch)
 hipError_t launch_pbkdf2(const uint32_t* mid, uint32_t cap, uint32_t base, uint32_t count, const uint32_t* counter,

@@ -375,6 +375,59 @@ def crack_combinator(hash_file, left, right, amp_side: int = L.DWPA_COMBI_AMP_RI
     return rc, [int(st[0]), int(st[1])]
 
 
+def _radices(radices):
+    r = [_u64(v, "radix") for v in radices]
+    return (ctypes.c_uint64 * max(1, len(r)))(*r), len(r)
+
+
+def chain_keyspace(radices) -> int:
+    """Keyspace of a chain (host only): the product of its parts' radices -- a list's word count, a mask's keyspace.
+    Raises DwpaError(DWPA_E_ARG) for no part, more than four, or a product above 2**64 - 1."""
+    arr, n = _radices(radices)
+    k = ctypes.c_uint64(0)
+    L.check(L.load().dwpa_chain_keyspace(arr, n, ctypes.byref(k)), "chain_keyspace")
+    return k.value
+
+
+def chain_split(radices, index: int) -> list:
+    """The digits of candidate `index` of a chain (host only), one per part, last part fastest: a list's word index,
+    a mask part's own index.  Raises DwpaError(DWPA_E_ARG) as chain_keyspace does, and for index >= keyspace."""
+    arr, n = _radices(radices)
+    d = (ctypes.c_uint64 * max(1, n))()
+    L.check(L.load().dwpa_chain_split(arr, n, _u64(index, "index"), d), "chain_split")
+    return [int(d[i]) for i in range(n)]
+
+
+def chain_candidate(parts, index: int, custom=()) -> bytes:
+    """Candidate `index` of a chain (host only).  parts: one entry per part, a sequence of words (bytes) for a list
+    or ("mask", MASK) for a mask; the parts' choices at chain_split's digits, joined left to right.  Unfiltered."""
+    parts = list(parts)
+    masks = [isinstance(p, tuple) and len(p) == 2 and p[0] == "mask" for p in parts]
+    radices = [mask_keyspace(p[1], custom) if m else len(p) for p, m in zip(parts, masks)]
+    digits = chain_split(radices, index)
+    return b"".join(mask_candidate(p[1], d, custom) if m else _b(p[d]) for p, m, d in zip(parts, masks, digits))
+
+
+def crack_chain(hash_file, parts, custom=(), skip: int = 0, limit: int = 0, nonce_error_corrections: int = 8,
+                out_file="help_crack.key", device_mask: int = 0, batch: int = 0, nc_mode: int = L.DWPA_NC_HASHCAT):
+    """The chain attack over hash_file, on every selected device.  parts: 1..4 entries (DWPA_CHAIN_LIST, path of a
+    plain or gzip word list) or (DWPA_CHAIN_MASK, mask); a candidate is one choice of every part joined left to right,
+    candidate id = its index in itertools.product order.  skip / limit: raw indices [skip, skip + limit) (limit 0 = to
+    the end).  Returns (rc, part_status): a hashcat exit code (0 cracked, 1 exhausted, -1 error) and one status per
+    part (DWPA_DICT_OK | DWPA_DICT_DAMAGED | DWPA_E_IO)."""
+    specs = [(int(k), _b(t)) for k, t in parts]
+    for k, t in specs:
+        if b"\0" in t:
+            raise L.DwpaError(L.DWPA_E_ARG, "crack_chain takes NUL-terminated texts: put a NUL byte into a custom set")
+    arr = (L.ChainSpec * max(1, len(specs)))(*[L.ChainSpec(k, t) for k, t in specs])
+    carr, keep = _custom(custom)
+    cfg = L.Config(ctypes.sizeof(L.Config), device_mask, batch, nc_mode)
+    st = (ctypes.c_int32 * max(1, len(specs)))()
+    rc = L.load().dwpa_crack_chain(_b(hash_file), arr, len(specs), carr, _u64(skip, "skip"), _u64(limit, "limit"),
+                                   _nc(nonce_error_corrections), _b(out_file), ctypes.byref(cfg), st)
+    return rc, [int(st[i]) for i in range(len(specs))]
+
+
 def crack_stats():
     """dwpa_crack_last_stats: {words, candidates, hashes, cracked, seconds, rules, rules_skipped, rules_rejmem} of
     this thread's last crack call."""
@@ -476,6 +529,37 @@ class Scan:
                                                     int(nbase), amp_off, amp_bytes, _u64(amp_words, "amp_words"),
                                                     _u64(amp_first, "amp_first"), int(amp_count), int(amp_side),
                                                     int(minlen), int(maxlen), stream), "scan_load_combinator")
+
+    def set_chain(self, parts, custom=()) -> int:
+        """Set the scan's chain: 1..4 parts, each (DWPA_CHAIN_LIST, d_offsets, d_bytes, nwords) -- an HBM-resident
+        list, which the caller keeps alive -- or (DWPA_CHAIN_MASK, mask).  custom: the sets ?1..?4 shared by the mask
+        parts.  Returns the chain's keyspace."""
+        parts = list(parts)
+        arr = (L.ChainPart * max(1, len(parts)))()
+        keep = []
+        for i, p in enumerate(parts):
+            arr[i].kind = int(p[0])
+            if arr[i].kind == L.DWPA_CHAIN_MASK:
+                m = _b(p[1])
+                keep.append(m)
+                arr[i].mask, arr[i].mask_len = m, len(m)
+            else:
+                arr[i].d_offsets, arr[i].d_bytes, arr[i].nwords = p[1], p[2], _u64(p[3], "nwords")
+        carr, ckeep = _custom(custom)
+        k = ctypes.c_uint64(0)
+        L.check(self._lib.dwpa_scan_set_chain(self._h, arr, len(parts), carr, ctypes.byref(k)), "scan_set_chain")
+        self.chain_keyspace = k.value
+        return k.value
+
+    def load_chain(self, first: int, count: int, minlen=8, maxlen=63, stream: int = 0):
+        """Raw chain candidates [first, first + count), generated and joined on the GPU.  A candidate is kept iff
+        every list word in it is at most 63 bytes and the total length is in minlen..maxlen; kept ones take compacted
+        slots in index order; candidate id = its raw index."""
+        for v, what in ((count, "count"), (minlen, "minlen"), (maxlen, "maxlen")):
+            if not 0 <= int(v) < 2**32:
+                raise L.DwpaError(L.DWPA_E_ARG, f"{what} {v} is outside uint32")
+        L.check(self._lib.dwpa_scan_load_chain(self._h, _u64(first, "first"), int(count), int(minlen), int(maxlen),
+                                               stream), "scan_load_chain")
 
     def pbkdf2(self, group: int = 0, stream: int = 0):
         L.check(self._lib.dwpa_scan_pbkdf2(self._h, group, stream), "scan_pbkdf2")

@@ -392,6 +392,53 @@ int dwpa_crack_combinator(const char *hash_file, const char *left_dict, const ch
                           int nonce_error_corrections, const char *out_file, const dwpa_config *cfg,
                           int32_t dict_status[2] /* nullable: left, right */);
 
+/* ---- chain attack: up to four word lists and masks joined left to right ------------------------------------------
+ * A chain is 1..DWPA_CHAIN_MAX_PARTS parts; each part is a word list held whole in device memory or a mask (the mask
+ * language above, 1..63 positions); a candidate is one choice of every part, concatenated in the order of the parts.
+ * It generalises the mask attack (one mask part), the hybrid attacks (list + mask, mask + list) and the combinator
+ * attack (list + list).  The custom sets ?1..?4 are shared by all mask parts of a chain.
+ * Radix and keyspace -- part p has N_p choices: a list's word count as read (every line counts, empty and overlong
+ * ones included, so an index names a line; N_p < 2^32, and text plus 8-byte offsets of at most
+ * DWPA_COMBI_AMP_MAX_BYTES per list), a mask's keyspace.  K = the product of the N_p, at most 2^64 - 1.  A part with
+ * N_p = 0 gives K = 0, which simply exhausts.
+ * Order and id -- candidate i is the mixed-radix numeral of i over the parts' radices with the LAST part fastest
+ * (itertools.product order); a mask part's own index is in this library's mask order.  Candidate id = i.  Parity with
+ * any hashcat order is unpinned, as for the other attacks.
+ * Filter: a candidate is kept iff every list word in it is <= 63 bytes and minlen <= total length <= maxlen (the
+ * crack call uses 8..63; a scan load treats maxlen above 64 as 64, one HMAC key block).  The decision is per
+ * candidate.  An empty word is an ordinary word.  Dropped candidates leave no slots.  Two ids can be the same string;
+ * both are candidates, and the crack call reports a line once, lowest id first.
+ * Left out: streaming a list too big to hold, rules on parts, increment, and filling a batch from several raw
+ * ranges -- a load is `batch` raw indices, so a chain whose filter drops most candidates runs short launches. */
+#define DWPA_CHAIN_LIST 0
+#define DWPA_CHAIN_MASK 1
+#define DWPA_CHAIN_MAX_PARTS 4
+/* Host only, no device.  dwpa_chain_keyspace: *keyspace = the product of radix[0..nparts) (0 if any radix is 0);
+ * DWPA_E_ARG: nparts outside 1..4, the product above 2^64 - 1.  dwpa_chain_split: digits[p] = the digit of `index`
+ * at part p (a list's word index, a mask part's own index), last part fastest; DWPA_E_ARG also for index >= K. */
+int dwpa_chain_keyspace(const uint64_t *radix, uint32_t nparts, uint64_t *keyspace);
+int dwpa_chain_split(const uint64_t *radix, uint32_t nparts, uint64_t index, uint64_t *digits);
+/* One part of dwpa_crack_chain.  DWPA_CHAIN_LIST: text is the path of a plain or gzip word list ($HEX[] words and
+ * CRLF as everywhere).  DWPA_CHAIN_MASK: text is a NUL-terminated mask. */
+typedef struct {
+    int kind;
+    const char *text;
+} dwpa_chain_spec;
+/* The chain over an m22000 hash file, with dwpa_crack_mask's hash file, rc convention, outfile records (the PSK
+ * rebuilt on the host from the id), nc-mode default and cfg handling.  Every list is read whole once, kept on the
+ * host and uploaded once per worker.  The workers (DWPA_CRACK_SHARDS_PER_DEVICE per selected device) take
+ * batch-sized ascending ranges of the raw indices [skip, skip + limit) (limit 0: to the end) from one shared cursor;
+ * lines cracked anywhere are retired on every worker, and the run stops when every line is cracked.
+ * DWPA_RC_ERROR before any device is touched: nparts outside 1..4, an unknown kind, an invalid mask, an unreadable
+ * list (its part_status entry is DWPA_E_IO), a list above the limits, K above 2^64 - 1, a missing hash file,
+ * skip >= K with K > 0.  part_status (nullable, nparts entries): DWPA_DICT_OK, DWPA_DICT_DAMAGED or DWPA_E_IO for a
+ * list, DWPA_DICT_OK for a mask.
+ * dwpa_crack_last_stats afterwards: words = the sum of the lists' word counts, candidates = kept candidates derived;
+ * dwpa_crack_worker_stats as for dwpa_crack_mask. */
+int dwpa_crack_chain(const char *hash_file, const dwpa_chain_spec *parts, uint32_t nparts, const dwpa_bytes custom[4],
+                     uint64_t skip, uint64_t limit, int nonce_error_corrections, const char *out_file,
+                     const dwpa_config *cfg, int32_t *part_status /* nullable, nparts entries */);
+
 /* hashcat rules (the whole rule language of hashcat >= 6.2.6: every mangling, reject and memory function; one
  * rule per line, '#' comments; semantics in dwpa_amd/csrc/rules.hpp and oracle/rules.py).  The text entry points
  * below (dwpa_rules_expand, dwpa_rules_apply_host, dwpa_rules_count, dwpa_scan_set_rules) are the interpreter and
@@ -489,6 +536,28 @@ int dwpa_scan_load_combinator(dwpa_scan *scan, const uint64_t *d_base_off, const
                               uint64_t first_base, uint32_t nbase, const uint64_t *d_amp_off,
                               const uint8_t *d_amp_bytes, uint64_t amp_words /* A */, uint64_t amp_first,
                               uint32_t amp_count, int amp_side, uint32_t minlen, uint32_t maxlen, void *hip_stream);
+/* Chain candidates ("chain attack" above).  A list part names an HBM-resident list (d_offsets: nwords + 1 byte
+ * offsets into d_bytes); a mask part names its mask text.  dwpa_scan_set_chain keeps the device pointers (the caller
+ * keeps the lists alive while the chain is set), uploads one 16 KiB table per mask part and stores K in *keyspace
+ * (nullable).  It leaves the mask of dwpa_scan_set_mask alone: a scan can hold both.  Setting a chain again replaces
+ * the previous one.  DWPA_E_ARG (the scan stays usable and keeps its previous chain): nparts 0 or above 4, an unknown
+ * kind, an invalid mask, nwords >= 2^32, K above 2^64 - 1.
+ * dwpa_scan_load_chain loads the raw indices [first, first + count): the kept ones compacted into slots in index
+ * order, ids[slot] = the raw index, dwpa_scan_loaded = the kept count.  A load does not synchronise with the host.
+ * A byte buffer needs no padding: only dwords that hold a byte of a kept word are read.  count == 0 loads nothing.
+ * DWPA_E_ARG: count > batch, first + count > K (wrap included), no chain set.  Without a device: DWPA_E_NODEV. */
+typedef struct {
+    int kind;                  /* DWPA_CHAIN_LIST or DWPA_CHAIN_MASK */
+    const uint64_t *d_offsets; /* list, in HBM */
+    const uint8_t *d_bytes;
+    uint64_t nwords;
+    const char *mask;          /* mask */
+    size_t mask_len;
+} dwpa_chain_part;
+int dwpa_scan_set_chain(dwpa_scan *scan, const dwpa_chain_part *parts, uint32_t nparts, const dwpa_bytes custom[4],
+                        uint64_t *keyspace);
+int dwpa_scan_load_chain(dwpa_scan *scan, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen,
+                         void *hip_stream);
 /* Stages 2 and 3 for ESSID group g (PMKs of the loaded batch, then every uncracked line of that ESSID). */
 int dwpa_scan_pbkdf2(dwpa_scan *scan, int group, void *hip_stream);
 int dwpa_scan_verify(dwpa_scan *scan, int group, void *hip_stream);
