@@ -12,6 +12,8 @@ OBJS := $(OBJ)/kernels.o $(OBJ)/rules_dev.o $(OBJ)/engine.o $(OBJ)/m22000_host.o
         $(OBJ)/combi_dev.o $(OBJ)/chain.o $(OBJ)/chain_dev.o $(OBJ)/crack_chain.o
 LLVM := /opt/rocm/lib/llvm/bin
 ISSUE_RULE ?= sched=1:alt:orig:asmnop,before_half
+# 1: the two work-queue PBKDF2 kernels keep their cold words in LDS (pbkdf2_dev.hpp pbkdf2_lane_lds); 0: the plain lane
+QUEUE_LDS ?= 1
 
 all: $(LIB) oracle
 
@@ -26,8 +28,9 @@ $(OBJ)/%.o: $(SRC)/%.cpp $(HDRS)
 # product PBKDF2 kernel: hipcc -> gfx950 asm -> VALU issue pass -> code object -> embedded byte array
 build/pbkdf2/pbkdf2_gfx950.s: $(SRC)/pbkdf2_gfx950.hip $(SRC)/pbkdf2_dev.hpp $(SRC)/crypto_dev.hpp
 	@mkdir -p build/pbkdf2
-	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 --cuda-device-only -S $< -o $@
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 --cuda-device-only -DDWPA_QUEUE_LDS=$(QUEUE_LDS) -S $< -o $@
 
+PBKDF2_QUEUE_KERNELS := k_pbkdf2_gfx950_q+k_pbkdf2_gfx950_mg_q
 PBKDF2_KERNELS := k_pbkdf2_gfx950+k_pbkdf2_gfx950_ms+k_pbkdf2_gfx950_mg+k_pbkdf2_gfx950_p+k_pbkdf2_gfx950_ms_p+k_pbkdf2_gfx950_mg_p+k_pbkdf2_gfx950_q+k_pbkdf2_gfx950_mg_q
 
 # the pass fails closed (an instruction it cannot model stops the build) ...
@@ -39,7 +42,15 @@ build/pbkdf2/issue_equiv.ok: build/pbkdf2/pbkdf2_gfx950.s build/pbkdf2/pbkdf2_is
 	python3 tools/issue_equiv.py $< $(PBKDF2_KERNELS) $(ISSUE_RULE) 2
 	@touch $@
 
-build/pbkdf2/pbkdf2_gfx950.hsaco: build/pbkdf2/pbkdf2_issue.s build/pbkdf2/issue_equiv.ok
+# ... and the LDS work-queue kernels must fit (64 VGPRs, no scratch, 8 waves per SIMD, 16 KiB LDS, five no-return LDS
+# xors and no memory access in the loop): a kernel that spills is not linked
+build/pbkdf2/queue_lds_gate.ok: build/pbkdf2/pbkdf2_issue.s tools/kernel_asm.py
+ifeq ($(QUEUE_LDS),1)
+	python3 tools/kernel_asm.py gate $< $(PBKDF2_QUEUE_KERNELS)
+endif
+	@touch $@
+
+build/pbkdf2/pbkdf2_gfx950.hsaco: build/pbkdf2/pbkdf2_issue.s build/pbkdf2/issue_equiv.ok build/pbkdf2/queue_lds_gate.ok
 	$(LLVM)/clang -target amdgcn-amd-amdhsa -mcpu=$(ARCH) -c $< -o build/pbkdf2/pbkdf2_issue.o
 	$(LLVM)/ld.lld -shared build/pbkdf2/pbkdf2_issue.o -o $@
 

@@ -179,19 +179,19 @@ constexpr int sched_cost(int T, int j) { return (sched_nv<M>(T, j) + (sched_cons
 #ifndef DWPA_SCHED_J2_MIN
 #define DWPA_SCHED_J2_MIN 64
 #endif
-template <class M>
+template <class M, int J2MIN = DWPA_SCHED_J2_MIN>
 constexpr int sched_form(int T) {
     int best = 0;
     for (int j = 1; j <= DWPA_SCHED_WIDE; j++)
-        if (T >= (16 << j) && (j < 2 || T >= DWPA_SCHED_J2_MIN) && sched_cost<M>(T, j) < sched_cost<M>(T, best))
+        if (T >= (16 << j) && (j < 2 || T >= J2MIN) && sched_cost<M>(T, j) < sched_cost<M>(T, best))
             best = j;
     return best;
 }
 
 // W[T] (T >= 16) of layout M from the full message array w[0..T-1] (compile-time indices: registers, not memory).
-template <class M, int T>
+template <class M, int T, int J2MIN = DWPA_SCHED_J2_MIN>
 __device__ __forceinline__ uint32_t sched_w(const uint32_t w[80]) {
-    constexpr int j = sched_form<M>(T), sh = 1 << j;
+    constexpr int j = sched_form<M, J2MIN>(T), sh = 1 << j;
     constexpr int s0 = T - 3 * sh, s1 = T - 8 * sh, s2 = T - 14 * sh, s3 = T - 16 * sh;
     constexpr uint32_t K = sched_const<M>(T, j);
     constexpr int nv = sched_nv<M>(T, j);
@@ -226,7 +226,7 @@ __device__ __forceinline__ void spacer() {
     if constexpr ((NOP & WHERE) != 0) asm volatile("s_nop 0");
 }
 
-template <class M, int T, int NOP = 0>
+template <class M, int T, int NOP = 0, int J2MIN = DWPA_SCHED_J2_MIN>
 __device__ __forceinline__ void step_m(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t& e, uint32_t w[80]) {
     uint32_t f;
     if constexpr (T < 20) f = ch3(b, c, d);
@@ -240,7 +240,7 @@ __device__ __forceinline__ void step_m(uint32_t& a, uint32_t& b, uint32_t& c, ui
         uint32_t wt;
         if constexpr (T < 16) wt = w[T];
         else {
-            wt = sched_w<M, T>(w);
+            wt = sched_w<M, T, J2MIN>(w);
             spacer<NOP, 1>();
             w[T] = wt;
         }
@@ -251,16 +251,16 @@ __device__ __forceinline__ void step_m(uint32_t& a, uint32_t& b, uint32_t& c, ui
     spacer<NOP, 4>();
 }
 
-template <class M, int NOP, int T0, int... Ts>
+template <class M, int NOP, int J2MIN, int T0, int... Ts>
 __device__ __forceinline__ void steps_m(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t& e, uint32_t w[80],
                                         std::integer_sequence<int, T0, Ts...>) {
-    step_m<M, T0, NOP>(a, b, c, d, e, w);
-    if constexpr (sizeof...(Ts) > 0) steps_m<M, NOP>(a, b, c, d, e, w, std::integer_sequence<int, Ts...>{});
+    step_m<M, T0, NOP, J2MIN>(a, b, c, d, e, w);
+    if constexpr (sizeof...(Ts) > 0) steps_m<M, NOP, J2MIN>(a, b, c, d, e, w, std::integer_sequence<int, Ts...>{});
 }
-template <class M, int Lo, int NOP, int... Is>
+template <class M, int Lo, int NOP, int J2MIN = DWPA_SCHED_J2_MIN, int... Is>
 __device__ __forceinline__ void run_steps_m(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d, uint32_t& e,
                                             uint32_t w[80], std::integer_sequence<int, Is...>) {
-    steps_m<M, NOP>(a, b, c, d, e, w, std::integer_sequence<int, (Lo + Is)...>{});
+    steps_m<M, NOP, J2MIN>(a, b, c, d, e, w, std::integer_sequence<int, (Lo + Is)...>{});
 }
 
 // out <- SHA1_compress(M, in[0..4] || 0x80 || 0.. || bitlen(64+20)): the PBKDF2/HMAC inner-loop compression
@@ -277,6 +277,41 @@ __device__ __forceinline__ void sha1_84(const Sha1Mid& M, const uint32_t in[5], 
     uint32_t a = a2, b = a1, c = M.r0, d = M.r1, e = M.h2;
     run_steps_m<Msg84, 2, NOP>(a, b, c, d, e, w, std::make_integer_sequence<int, 78>{});
     out[0] = M.h0 + a; out[1] = M.h1 + b; out[2] = M.h2 + c; out[3] = M.h3 + d; out[4] = M.h4 + e;
+}
+
+// sha1_84 with the digest addends h0, h1, h3, h4 parked in LDS (the work-queue PBKDF2 kernels, pbkdf2_dev.hpp
+// pbkdf2_lane_lds): they are read only here, after the last schedule word, when the j = 2 operands are dead, so a
+// compression holds four VGPRs fewer across its rounds.  `cold` points at this lane's column of a [word][STRIDE]
+// LDS array holding h0, h1, h3, h4 in that order.  The reads are relaxed atomic loads: the compiler may not hoist
+// them out of the 4096 loop (the values would be back in VGPRs), yet, unlike volatile loads, it does not wait for
+// each one before it issues the next.  J2MIN is the first t that may use the j = 2 schedule form
+// (DWPA_SCHED_J2_MIN everywhere else).
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+__device__ __forceinline__ uint32_t lds_get(lds_u32* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void lds_put(lds_u32* p, uint32_t v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+template <int J2MIN, int STRIDE>
+__device__ __forceinline__ void sha1_84_lds(const Sha1Mid& M, lds_u32* cold, const uint32_t in[5],
+                                            uint32_t out[5]) {
+    uint32_t w[80];
+    w[0] = in[0]; w[1] = in[1]; w[2] = in[2]; w[3] = in[3]; w[4] = in[4];
+#pragma unroll
+    for (int i = 5; i < 16; i++) w[i] = w84_const(i);
+    uint32_t a1 = M.c0 + w[0];
+    uint32_t a2 = rotl(a1, 5) + M.c1 + w[1];
+    uint32_t a = a2, b = a1, c = M.r0, d = M.r1, e = M.h2;
+    step_m<Msg84, 2, 0, J2MIN>(a, b, c, d, e, w);
+    // No instruction: w[2] now depends on round 2's result, so the schedule words that read it (W16, W18, which the
+    // compiler otherwise hoists to the loop's top now that W0..W4 stay live up to t = 68) follow round 2.  The loop
+    // then opens with round 2's Ch like every other PBKDF2 kernel's, which the operand-swap mutation of
+    // tests/test_issue_pass_equiv.py relies on (a swapped XOR3 computes the same value), and one VGPR fewer is live.
+    asm("" : "+v"(w[2]) : "v"(a));
+    run_steps_m<Msg84, 3, 0, J2MIN>(a, b, c, d, e, w, std::make_integer_sequence<int, 77>{});
+    out[0] = lds_get(cold) + a; out[1] = lds_get(cold + STRIDE) + b; out[2] = M.h2 + c;
+    out[3] = lds_get(cold + 2 * STRIDE) + d; out[4] = lds_get(cold + 3 * STRIDE) + e;
 }
 
 // Compression of a wave-uniform message block whose schedule the host has expanded: kw[t] = K_t + W_t for t < 80

@@ -29,11 +29,15 @@ Rules (comma-separated, applied in the loop body only):
                   inline-asm blocks where provably dead (drop_asm_nops); `bank` then renames loop-local values so that fewer
                   v_bitop3_b32 read sources from one VGPR bank (bank_rename; A/B only, profiles/r05/vgpr_bank/).
                   Applied before the nop rules (A/B).  Fails closed: an instruction outside SCHED_VALU (a second
-                  destination, an implicit operand, a transcendental op, DPP/SDWA) stops the build
+                  destination, an implicit operand, a transcendental op, DPP/SDWA) stops the build.  LDS
+                  instructions (ds_read_b32, no-return ds_xor_b32, ds_write_b32) and s_waitcnt lgkmcnt(N) are fixed
+                  points: they keep their order, issue once the VALUs the compiler placed in front of them have
+                  issued, and a read's consumers stay behind the wait that retires it (reschedule); any other ds_
+                  instruction, wait counter or memory instruction stops the build
   none            copy through
 
 The Makefile runs tools/issue_equiv.py on every scheduled kernel after the pass: the scheduled loop body must compute
-the same registers as the compiler's on random inputs, or the build stops.
+the same registers and the same LDS words as the compiler's on random inputs, or the build stops.
 """
 import re
 import sys
@@ -132,8 +136,14 @@ def _safe_valu(line):
 def _defs_uses(line):
     """(op, defs, uses) of one loop-body instruction; None for a line that is not an instruction.  Raises ValueError
     for anything the list schedule cannot prove safe to move (see SCHED_VALU): the pass then fails the build."""
+    lds = _lds_defs_uses(line)
+    if lds:
+        return lds
     m = re.match(r"\s+([vs]_\w+)\s*(.*)", line)
     if not m:
+        s = line.strip()
+        if s and not s.startswith((";", ".")) and not s.endswith(":"):
+            raise ValueError(f"unexpected instruction in the loop body: {line!r}")
         return None
     op = m.group(1)
     if op.startswith("v_"):
@@ -145,7 +155,61 @@ def _defs_uses(line):
         return op, {"scc"}, {r for r in regs if r}
     if op in ("s_add_i32", "s_sub_i32", "s_add_u32", "s_sub_u32"):
         return op, {regs[0], "scc"}, {r for r in regs[1:] if r}
+    if op == "s_waitcnt":
+        lds_wait_count(line)  # only the LDS counter; the registers it releases are filled in by reschedule
+        return op, set(), set()
     raise ValueError(f"unexpected instruction in the loop body: {line!r}")
+
+
+# The LDS instructions a loop body may hold (the work-queue kernels' cold words, pbkdf2_dev.hpp pbkdf2_lane_lds): one
+# dword per lane, a VGPR address and an immediate offset, nothing else.  A read defines its destination; the
+# no-return xor and the write define no register.  Anything else that starts with ds_ stops the build.
+_DS_FORMS = {"ds_read_b32": ("d", "a"), "ds_xor_b32": ("a", "s"), "ds_write_b32": ("a", "s")}
+
+
+def lds_op(line):
+    """(op, dst or None, address VGPR, data VGPR or None, offset) of an LDS instruction the pass models; None for a
+    line that is no ds_ instruction; ValueError for any other ds_ instruction or operand form."""
+    m = re.match(r"\s+(ds_\w+)\s+(.*)$", line)
+    if not m:
+        return None
+    op, rest = m.group(1), m.group(2).split(";")[0].strip()
+    if op not in _DS_FORMS:
+        raise ValueError(f"LDS instruction the pass does not model: {line!r}")
+    parts = [p.strip() for p in rest.split(",")]
+    last = parts[-1].split()
+    parts[-1] = last[0]
+    off = 0
+    for mod in last[1:]:
+        mm = re.fullmatch(r"offset:(\d+)", mod)
+        if not mm:
+            raise ValueError(f"LDS modifier the pass does not model ({mod}): {line!r}")
+        off = int(mm.group(1))
+    form = _DS_FORMS[op]
+    if len(parts) != len(form) or not all(_vgpr(p) for p in parts):
+        raise ValueError(f"LDS operands the pass does not model: {line!r}")
+    f = dict(zip(form, parts))
+    return op, f.get("d"), f["a"], f.get("s"), off
+
+
+def lds_wait_count(line):
+    """N of `s_waitcnt lgkmcnt(N)`; any other counter in a loop body stops the build."""
+    m = re.fullmatch(r"\s+s_waitcnt\s+lgkmcnt\((\d+)\)\s*(;.*)?", line)
+    if not m:
+        raise ValueError(f"wait the pass does not model: {line!r}")
+    return int(m.group(1))
+
+
+def _lds_defs_uses(line):
+    d = lds_op(line)
+    if d is None:
+        return None
+    op, dst, addr, data, _ = d
+    return op, ({dst} if dst else set()), ({addr, data} if data else {addr})
+
+
+def _is_fixed(op):
+    return op.startswith("ds_") or op == "s_waitcnt"
 
 
 def drop_asm_nops(body):
@@ -190,10 +254,35 @@ def reschedule(body, dmin, alt, group=False, orig=False):
         if du:
             ins.append((l,) + du)
     n = len(ins)
+    # LDS instructions and waits are fixed points: they keep their order among themselves, so every lgkmcnt(N) still
+    # counts the same operations.  A wait releases the destinations of the reads it retires (N outstanding LDS
+    # operations stay): it is modelled as reading and writing those registers, which keeps a read's consumers behind
+    # the wait and the read itself, and every producer of an LDS operand, in front of its instruction.  Until the
+    # wait no VALU may touch such a register, and no read may be left outstanding at the loop's end.
+    pending = []  # destinations (None for xor / write) of the outstanding LDS operations, oldest first
+    for k, (l, op, defs, uses) in enumerate(ins):
+        if op == "s_waitcnt":
+            keep = min(lds_wait_count(l), len(pending))
+            done, pending = pending[:len(pending) - keep], pending[len(pending) - keep:]
+            regs = {r for r in done if r}
+            ins[k] = (l, op, regs, set(regs))
+        elif op.startswith("ds_"):
+            if (defs | uses) & {r for r in pending if r}:
+                raise ValueError(f"LDS instruction touches the destination of an outstanding LDS read: {l!r}")
+            pending.append(next(iter(defs), None))
+        elif (defs | uses) & {r for r in pending if r}:
+            raise ValueError(f"instruction touches the destination of an LDS read before the wait: {l!r}")
+    if any(pending):
+        raise ValueError("an LDS read is still outstanding at the end of the loop body")
     preds = [set() for _ in range(n)]
     raw = [set() for _ in range(n)]
     last_w, readers = {}, {}
+    prev_fixed = None
     for i, (_, op, defs, uses) in enumerate(ins):
+        if _is_fixed(op):
+            if prev_fixed is not None:
+                preds[i].add(prev_fixed)
+            prev_fixed = i
         for r in uses:
             if r in last_w:
                 preds[i].add(last_w[r])
@@ -209,7 +298,7 @@ def reschedule(body, dmin, alt, group=False, orig=False):
         for r in defs:
             last_w[r] = i
             readers[r] = set()
-    salu = [i for i in range(n) if ins[i][1].startswith("s_")]
+    salu = [i for i in range(n) if ins[i][1].startswith("s_") and ins[i][1] != "s_waitcnt"]
     for i in salu:  # the loop counter stays at the end, next to the branch
         for j in range(n):
             if j not in salu and (ins[i][2] & (ins[j][2] | ins[j][3]) - {"scc"}):
@@ -224,17 +313,29 @@ def reschedule(body, dmin, alt, group=False, orig=False):
     left = [len(preds[i]) for i in range(n)]
     ready = {i for i in range(n) if not left[i] and i not in salu}
     pos, order, prev_half = {}, [], None
+    # A fixed point issues once every VALU the compiler placed in front of it has issued, and then at once: it keeps
+    # the compiler's distance between an LDS read and its wait.  Those VALUs never depend on it, so this cannot stall.
+    fixed = {i for i in range(n) if _is_fixed(ins[i][1])}
+    movable = [i for i in range(n) if i not in fixed and i not in salu]
+    lo = 0  # movable[lo] is the first VALU, in the compiler's order, that has not issued
     while ready:
         def key(i):
             dist = min((len(order) - pos[j] for j in raw[i]), default=dmin)
             half = ins[i][1].replace("_e32", "").replace("_e64", "") in HALF
             return (min(dist, dmin), alt and prev_half is not None and half != prev_half,
                     group and prev_half is not None and half == prev_half, *((-i, cp[i]) if orig else (cp[i], -i)))
-        i = max(ready, key=key)
+        while lo < len(movable) and movable[lo] in pos:
+            lo += 1
+        due = [i for i in ready if i in fixed and (lo == len(movable) or movable[lo] > i)]
+        free = [i for i in ready if i not in fixed]
+        if not due and not free:
+            raise ValueError("schedule stalled at a fixed point")
+        i = min(due) if due else max(free, key=key)
         ready.discard(i)
         pos[i] = len(order)
         order.append(i)
-        prev_half = ins[i][1].replace("_e32", "").replace("_e64", "") in HALF
+        if not _is_fixed(ins[i][1]):  # an LDS instruction or a wait takes no VALU issue slot
+            prev_half = ins[i][1].replace("_e32", "").replace("_e64", "") in HALF
         for j in succs[i]:
             left[j] -= 1
             if not left[j] and j not in salu:
@@ -268,6 +369,14 @@ def bank_rename(body, maxv):
             continue
         parts = m.group(4).split(",")
         ops.append([m.group(2), parts, m.group(1) + m.group(2) + m.group(3)])
+
+    # registers an LDS instruction reads or writes keep their names and take no renamed value: a read's destination is
+    # written at its wait, not at the instruction, and this step does not model that
+    lds_regs = set()
+    for l in body:
+        d = lds_op(l)
+        if d:
+            lds_regs |= {r for r in d[1:4] if r}
 
     def tok(p):
         return p.strip().split()[0] if p.strip() else ""
@@ -328,7 +437,7 @@ def bank_rename(body, maxv):
         # try to move one source value of a conflicting pair to a bank none of the other sources use
         done = False
         for s in srcs:
-            if done or not _vgpr(s):
+            if done or not _vgpr(s) or s in lds_regs:
                 continue
             dl = max((j for j in range(k) if s in acc(j)[0]), default=None)
             if dl is None:
@@ -341,7 +450,7 @@ def bank_rename(body, maxv):
             others = {int(t[1:]) % 4 for t in srcs if _vgpr(t) and t != s}
             for r in range(maxv + 1):
                 nr = f"v{r}"
-                if r % 4 in others or nr == s or not free(nr, dl, last):
+                if r % 4 in others or nr == s or nr in lds_regs or not free(nr, dl, last):
                     continue
                 # the move must not add conflicts at the value's other bitop3 readers
                 old_c = sum(_bop3_conflicts([tok(p) for p in ops[j][1][1:]]) for j in uses if ops[j][0] == "v_bitop3_b32")

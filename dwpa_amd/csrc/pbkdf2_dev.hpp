@@ -65,6 +65,68 @@ __device__ __forceinline__ void pbkdf2_lane(const uint32_t hi[5], const uint32_t
     }
 }
 
+// pbkdf2_lane for the work-queue kernels: the lane's cold values live in static LDS, which frees the VGPRs the
+// j = 2 schedule forms need from t = 64 at 8 waves per SIMD (84 XOR-type ops per compression instead of 93).
+// Layout: cold[word][threadIdx.x], 1 KiB per word per 256-thread workgroup, bank = lane % 32 for every word, so a
+// b32 access never conflicts.  Words 0..4 hold T, 5..8 the inner midstate's h0, h1, h3, h4, 9..12 the outer's
+// (QL_WORDS = 13: 13 KiB per workgroup, 104 KiB for the 8 workgroups of a CU).
+//   T: written with U_1, then five no-return LDS xors per iteration (the LDS pipe is otherwise idle; the VALU
+//      stream loses its five v_xor), read back once after the loop.  DS operations of one wave complete in order,
+//      so the read-back sees every xor before it.
+//   h0, h1, h3, h4: a digest's addends, read at each compression's end (sha1_84_lds).
+// A lane touches only its own column, so nothing is shared between lanes and no barrier is needed; a wave's next
+// item overwrites the column from the top.  Lanes past the last slot never get here.
+constexpr int QL_T = 0, QL_MI = 5, QL_MO = 9, QL_WORDS = 13, QL_STRIDE = 256;
+constexpr int QL_J2_MIN = 64;
+
+__device__ __forceinline__ void pbkdf2_lane_lds(uint32_t (*cold_base)[QL_STRIDE], const uint32_t hi[5],
+                                                const uint32_t ho[5], const uint32_t* sb, uint32_t nsalt,
+                                                uint32_t t[5]) {
+    lds_u32* cold = (lds_u32*)&cold_base[0][threadIdx.x];  // LDS address space: ds_* with immediate offsets
+    uint32_t st[5] = {hi[0], hi[1], hi[2], hi[3], hi[4]};
+    for (uint32_t b = 0; b < nsalt; b++) {
+        uint32_t m[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) m[j] = sb[b * 16 + j];
+        sha1_compress(st, m);
+    }
+    const Sha1Mid MI = sha1_mid(hi);
+    const Sha1Mid MO = sha1_mid(ho);
+    lds_put(cold + (QL_MI + 0) * QL_STRIDE, MI.h0); lds_put(cold + (QL_MI + 1) * QL_STRIDE, MI.h1);
+    lds_put(cold + (QL_MI + 2) * QL_STRIDE, MI.h3); lds_put(cold + (QL_MI + 3) * QL_STRIDE, MI.h4);
+    lds_put(cold + (QL_MO + 0) * QL_STRIDE, MO.h0); lds_put(cold + (QL_MO + 1) * QL_STRIDE, MO.h1);
+    lds_put(cold + (QL_MO + 2) * QL_STRIDE, MO.h3); lds_put(cold + (QL_MO + 3) * QL_STRIDE, MO.h4);
+    uint32_t u[5], x[5];
+    sha1_84_lds<QL_J2_MIN, QL_STRIDE>(MO, cold + QL_MO * QL_STRIDE, st, u);
+#pragma unroll
+    for (int k = 0; k < 5; k++) lds_put(cold + (QL_T + k) * QL_STRIDE, u[k]);
+#pragma unroll 1
+    for (int it = 1; it < 4096; it++) {
+        sha1_84_lds<QL_J2_MIN, QL_STRIDE>(MI, cold + QL_MI * QL_STRIDE, u, x);
+        sha1_84_lds<QL_J2_MIN, QL_STRIDE>(MO, cold + QL_MO * QL_STRIDE, x, u);
+#pragma unroll
+        for (int k = 0; k < 5; k++)  // result unused: ds_xor_b32 without return
+            __hip_atomic_fetch_xor(cold + (QL_T + k) * QL_STRIDE, u[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+#pragma unroll
+    for (int k = 0; k < 5; k++) t[k] = lds_get(cold + (QL_T + k) * QL_STRIDE);
+}
+
+// The lane of the two work-queue kernels.  DWPA_QUEUE_LDS=0 builds them with the plain pbkdf2_lane (every value in
+// VGPRs, j = 2 from DWPA_SCHED_J2_MIN) for A/B runs and for the check that nothing else changed.
+#ifndef DWPA_QUEUE_LDS
+#define DWPA_QUEUE_LDS 1
+#endif
+__device__ __forceinline__ void pbkdf2_lane_queue(const uint32_t hi[5], const uint32_t ho[5], const uint32_t* sb,
+                                                  uint32_t nsalt, uint32_t t[5]) {
+#if DWPA_QUEUE_LDS
+    __shared__ uint32_t cold[QL_WORDS][QL_STRIDE];
+    pbkdf2_lane_lds(cold, hi, ho, sb, nsalt, t);
+#else
+    pbkdf2_lane(hi, ho, sb, nsalt, t);
+#endif
+}
+
 __device__ __forceinline__ void set_wave_prio(uint32_t p) {
     switch (p) {  // s_setprio takes an immediate
     case 0: __builtin_amdgcn_s_setprio(0); break;
@@ -189,7 +251,7 @@ __device__ __forceinline__ void pbkdf2_body_queue(const uint32_t* __restrict__ m
         if (s < n) {
             uint32_t hi[5], ho[5], t[5];
             load_mid(mid, cap, s, hi, ho);
-            pbkdf2_lane(hi, ho, salt + (size_t)blk * nsalt * 16, nsalt, t);
+            pbkdf2_lane_queue(hi, ho, salt + (size_t)blk * nsalt * 16, nsalt, t);
             store_block(pmk, cap, s, blk, t);
         }
     }
@@ -258,7 +320,7 @@ __device__ __forceinline__ void pbkdf2_body_mg_queue(const uint32_t* __restrict_
             uint32_t hi[5], ho[5], t[5];
             load_mid(mid, cap, s, hi, ho);
             const uint32_t off = gsalt[2 * c], nsalt = gsalt[2 * c + 1];
-            pbkdf2_lane(hi, ho, salt + off + (size_t)blk * nsalt * 16, nsalt, t);
+            pbkdf2_lane_queue(hi, ho, salt + off + (size_t)blk * nsalt * 16, nsalt, t);
             store_block(pmk + (size_t)c * cap, pstride, s, blk, t);
         }
     }

@@ -6,6 +6,11 @@
 // loop iteration, 64 VGPRs, no spill): with the issue pass's list scheduler they measured -0.9 % at 8 waves per SIMD
 // and -0.3 % at 6 against j <= 1 (profiles/r05/sched_identities/).  The lone-wave kernels in kernels.hip keep
 // j <= 1, which is faster there (one-key call 8.17 against 8.29 ms).
+//
+// The two work-queue kernels (_q, _mg_q) take j = 2 from round 64: their lane keeps T and eight digest addends in
+// LDS (pbkdf2_dev.hpp pbkdf2_lane_lds), which frees the VGPRs the forms for t = 64..72 need: 1,092 VALU per loop
+// iteration, 62 VGPRs, 13 KiB LDS per workgroup, no spill.  The other six kernels are the check path's PBKDF2 head,
+// which shares its CUs with the keyver-3 verifier's 32 KiB of LDS, and stay as they were.
 #ifndef DWPA_SCHED_WIDE
 #define DWPA_SCHED_WIDE 2
 #endif
