@@ -196,6 +196,8 @@ SIGNATURES = {
     "dwpa_event_elapsed_ms": ([_P, _P, ctypes.POINTER(ctypes.c_float)], ctypes.c_int),
     "dwpa_event_destroy": ([_P], ctypes.c_int),
     "dwpa_debug_pbkdf2_kernels": ([ctypes.c_int], ctypes.c_uint32),  # test hook, not in include/dwpa22000.h
+    "dwpa_debug_verify_kernels": ([ctypes.c_int], ctypes.c_uint32),  # test hook, not in include/dwpa22000.h
+    "dwpa_debug_check_hit_records": ([ctypes.c_int], ctypes.c_uint64),  # test hook, not in include/dwpa22000.h
 }
 
 # Bit i of dwpa_debug_pbkdf2_kernels' mask (csrc/kernels.hpp Pbkdf2Kernel): the hipcc-scheduled kernels of kernels.hip,
@@ -204,6 +206,13 @@ PBKDF2_KERNEL_NAMES = ("k_pbkdf2", "k_pbkdf2_ms", "k_pbkdf2_mg", "k_pbkdf2_ms_ta
                        "k_pbkdf2_gfx950", "k_pbkdf2_gfx950_ms", "k_pbkdf2_gfx950_mg",
                        "k_pbkdf2_gfx950_p", "k_pbkdf2_gfx950_ms_p", "k_pbkdf2_gfx950_mg_p",
                        "k_pbkdf2_gfx950_q", "k_pbkdf2_gfx950_mg_q")
+
+# Bit i of dwpa_debug_verify_kernels' mask (csrc/kernels.hpp verify_kernel_bit): the key-parallel kernel's classes
+# (PMKID, keyver 1, 2, 3, 1|2 combined, all four: the scan path's mixed launches), then the attempt-parallel pair
+# k_eapol_keys + k_verify_att of the same classes (EAPOL lines with >= 64 attempts on the check path).
+VERIFY_KERNEL_NAMES = ("k_verify<pmkid>", "k_verify<kv1>", "k_verify<kv2>", "k_verify<kv3>", "k_verify<kv1|kv2>",
+                       "k_verify<all>", "k_verify_att<pmkid>", "k_verify_att<kv1>", "k_verify_att<kv2>",
+                       "k_verify_att<kv3>", "k_verify_att<kv1|kv2>", "k_verify_att<all>")
 
 _lib = None
 
@@ -229,6 +238,20 @@ def pbkdf2_kernels(reset: bool = False) -> frozenset:
     mask = int(load().dwpa_debug_pbkdf2_kernels(1 if reset else 0))
     assert mask >> len(PBKDF2_KERNEL_NAMES) == 0, hex(mask)
     return frozenset(n for i, n in enumerate(PBKDF2_KERNEL_NAMES) if mask >> i & 1)
+
+
+def verify_kernels(reset: bool = False) -> frozenset:
+    """Names of the verify kernels this process has launched since the last reset (the library's test hook): which
+    verifier, key-parallel k_verify or attempt-parallel k_verify_att, and which class of it a call really ran."""
+    mask = int(load().dwpa_debug_verify_kernels(1 if reset else 0))
+    assert mask >> len(VERIFY_KERNEL_NAMES) == 0, hex(mask)
+    return frozenset(n for i, n in enumerate(VERIFY_KERNEL_NAMES) if mask >> i & 1)
+
+
+def check_hit_records(reset: bool = False) -> int:
+    """Hit records the device check path has read back in this process since the last reset (test hook): every
+    matching (key, attempt) item the verify kernels reported, where dwpa_check_stats.hits counts jobs with a hit."""
+    return int(load().dwpa_debug_check_hit_records(1 if reset else 0))
 
 
 def check(rc: int, what: str = "") -> int:

@@ -1041,6 +1041,10 @@ static int queue_verify(Device& d, const SlotTable& T, size_t base, size_t b, si
     return 0;
 }
 
+// Hit records the check path has read back from the device in this process (dwpa_debug_check_hit_records, a test
+// hook): dwpa_check_stats.hits counts jobs with a hit, not the records the verifiers wrote.
+static std::atomic<uint64_t> g_check_hit_records{0};
+
 // Wait for the derive + verify kernels of one chunk (both streams) and append their hits.
 static int collect_hits(Device& d, std::vector<HitDev>& hits_out) {
     PhaseTrace tr;
@@ -1054,6 +1058,7 @@ static int collect_hits(Device& d, std::vector<HitDev>& hits_out) {
     tr.mark("  device wait");
     const uint32_t nh = *(volatile const uint32_t*)d.hits_host.p;
     d.stats.tail_waves_raised += *((volatile const uint32_t*)d.hits_host.p + 1);
+    g_check_hit_records.fetch_add(nh, std::memory_order_relaxed);
     if (nh > d.batch.hitcap) return DWPA_E_OVERFLOW;
     size_t old = hits_out.size();
     hits_out.resize(old + nh);
@@ -1950,6 +1955,20 @@ int dwpa_abi_version(void) { return DWPA_ABI_VERSION; }
 uint32_t dwpa_debug_pbkdf2_kernels(int reset) {
     return reset ? g_pbkdf2_kernels.exchange(0u, std::memory_order_relaxed)
                  : g_pbkdf2_kernels.load(std::memory_order_relaxed);
+}
+
+// The same for the verify kernels (kernels.hpp verify_kernel_bit): which verifier, key-parallel or attempt-parallel,
+// and which class of it this process has launched.
+uint32_t dwpa_debug_verify_kernels(int reset) {
+    return reset ? g_verify_kernels.exchange(0u, std::memory_order_relaxed)
+                 : g_verify_kernels.load(std::memory_order_relaxed);
+}
+
+// And the hit records the check path's verify kernels wrote and the host read back (every matching (key, attempt)
+// item: two for a key whose LE and BE attempt are one value), summed over the process's check calls.
+uint64_t dwpa_debug_check_hit_records(int reset) {
+    return reset ? g_check_hit_records.exchange(0u, std::memory_order_relaxed)
+                 : g_check_hit_records.load(std::memory_order_relaxed);
 }
 
 int dwpa_init(const dwpa_config* cfg) {

@@ -606,6 +606,8 @@ __global__ __launch_bounds__(vc_block(VC)) __attribute__((amdgpu_waves_per_eu(vc
 // ------------------------------------------------------------------------------------------------
 static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
+std::atomic<uint32_t> g_verify_kernels{0};
+
 hipError_t launch_prep_dict(const uint64_t* off, const uint8_t* bytes, uint64_t first, uint32_t count, uint32_t minlen,
                             uint32_t maxlen, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
                             bool compact, hipStream_t s) {
@@ -711,7 +713,8 @@ hipError_t launch_verify(const uint32_t* pmk, uint32_t cap, const uint64_t* ids,
                          uint32_t pstride) {
     if (nsegs == 0 || nlines == 0) return hipSuccess;
     if (!pstride) pstride = cap;
-#define DWPA_LAUNCH_VERIFY(V)                                                                                  \
+    note_verify_kernel(vc, false);
+#define DWPA_LAUNCH_VERIFY(V)                                                                                 \
     hipLaunchKernelGGL(k_verify<V>, dim3(cdiv(nsegs, vc_block(V) / 64), segs ? 1 : nlines), dim3(vc_block(V)),  \
                        0, s, pmk, cap, ids, counter, segs, nsegs, line_base, line_list, line_poff, pstride, lines,  \
                        pool, atts, hits, hitcnt, hitcap)
@@ -728,6 +731,7 @@ hipError_t launch_verify_att(const uint32_t* pmk, uint32_t cap, const uint64_t* 
                              uint32_t* hitcnt, uint32_t hitcap, uint32_t* first_hit, uint32_t vc, hipStream_t s) {
     if (nsegs == 0 || nwaves == 0) return hipSuccess;
     if (segk < 1 || segk > 64 || kstride < (uint64_t)nsegs * segk) return hipErrorInvalidValue;
+    note_verify_kernel(vc & ~VC_PMKID, true);
 #define DWPA_LAUNCH_VERIFY_ATT(V)                                                                                 \
     hipLaunchKernelGGL(k_eapol_keys<V>, dim3(cdiv((uint64_t)nsegs * 64, 256)), dim3(256), 0, s, pmk, cap, segs,   \
                        nsegs, lines, pool, keys, kstride, segk);                                                   \

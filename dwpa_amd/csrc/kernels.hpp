@@ -88,6 +88,20 @@ enum Pbkdf2Kernel : uint32_t {
 };
 extern std::atomic<uint32_t> g_pbkdf2_kernels;
 inline void note_pbkdf2_kernel(uint32_t bit) { g_pbkdf2_kernels.fetch_or(bit, std::memory_order_relaxed); }
+// Which verify kernels this process has launched, the same way (dwpa_debug_verify_kernels): one bit per mode
+// (key-parallel k_verify, attempt-parallel k_eapol_keys + k_verify_att) and instantiated class, so a test sees which
+// verifier a line took.  The bit order is VERIFY_KERNEL_NAMES in dwpa_amd/_lib.py: the classes of DWPA_VC_DISPATCH
+// (PMKID, keyver 1, 2, 3, 1|2, all) key-parallel, then the same attempt-parallel.
+constexpr uint32_t VK_ATT_SHIFT = 6;
+inline uint32_t verify_kernel_bit(uint32_t vc, bool att) {
+    const uint32_t c = vc == VC_PMKID ? 0u : vc == VC_KV1 ? 1u : vc == VC_KV2 ? 2u : vc == VC_KV3 ? 3u
+                       : vc == (VC_KV1 | VC_KV2) ? 4u : 5u;
+    return 1u << (c + (att ? VK_ATT_SHIFT : 0u));
+}
+extern std::atomic<uint32_t> g_verify_kernels;
+inline void note_verify_kernel(uint32_t vc, bool att) {
+    g_verify_kernels.fetch_or(verify_kernel_bit(vc, att), std::memory_order_relaxed);
+}
 // PMKs that give every SIMD of the current device one PBKDF2 wave (two output-block lanes per PMK); 0 on error
 uint32_t pbkdf2_wave_unit();
 // many ESSIDs per launch: slot s uses the salt entry pool + sref[s] = {nsalt, [2][nsalt][16] words}

@@ -56,6 +56,31 @@ def test_debug_pbkdf2_kernels_hook():
     assert r.stdout.strip() == "0 0 []"
 
 
+def test_debug_verify_kernels_hook():
+    """dwpa_debug_verify_kernels and dwpa_debug_check_hit_records (the test hooks tests/test_gpu_check_recall.py reads
+    from which verifier a check call ran and how many hit records it wrote): exported, outside the public header,
+    the PHP cdef and the ABI version, and empty in a process that has launched nothing."""
+    import subprocess
+    import sys
+    lib = L.load()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    php = open(os.path.join(root, "php", "dwpa22000.php")).read()
+    for hook in ("dwpa_debug_verify_kernels", "dwpa_debug_check_hit_records"):
+        assert hasattr(lib, hook)
+        assert hook not in declared_symbols() and hook not in open(L.HEADER).read() and hook not in php
+    assert lib.dwpa_abi_version() == 4
+    names = L.VERIFY_KERNEL_NAMES
+    assert len(names) == len(set(names)) == 12
+    assert [n.split("<")[1] for n in names[:6]] == [n.split("<")[1] for n in names[6:]]  # the same classes twice
+    assert all(n.startswith("k_verify<") for n in names[:6]) and all(n.startswith("k_verify_att<") for n in names[6:])
+    child = ("import sys; sys.path.insert(0, sys.argv[1]); from dwpa_amd import _lib as L; lib = L.load(); "
+             "print(lib.dwpa_debug_verify_kernels(0), lib.dwpa_debug_verify_kernels(1), sorted(L.verify_kernels()), "
+             "L.check_hit_records(), L.check_hit_records(reset=True))")
+    r = subprocess.run([sys.executable, "-c", child, root], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.strip() == "0 0 [] 0 0"
+
+
 def test_hc_unhex_matches_oracle():
     import dwpa_amd
     for k in [b"$HEX[414243]", b"$HEX[]", b"$HEX[41424]", b"$HEX[41zz]", b"$HEX[4142]x", b"plain", b"$HEX[00ff]",
