@@ -198,6 +198,7 @@ SIGNATURES = {
     "dwpa_debug_pbkdf2_kernels": ([ctypes.c_int], ctypes.c_uint32),  # test hook, not in include/dwpa22000.h
     "dwpa_debug_verify_kernels": ([ctypes.c_int], ctypes.c_uint32),  # test hook, not in include/dwpa22000.h
     "dwpa_debug_check_hit_records": ([ctypes.c_int], ctypes.c_uint64),  # test hook, not in include/dwpa22000.h
+    "dwpa_debug_scan_work": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_int], None),  # test hook, not in the header
 }
 
 # Bit i of dwpa_debug_pbkdf2_kernels' mask (csrc/kernels.hpp Pbkdf2Kernel): the hipcc-scheduled kernels of kernels.hip,
@@ -252,6 +253,18 @@ def check_hit_records(reset: bool = False) -> int:
     """Hit records the device check path has read back in this process since the last reset (test hook): every
     matching (key, attempt) item the verify kernels reported, where dwpa_check_stats.hits counts jobs with a hit."""
     return int(load().dwpa_debug_check_hit_records(1 if reset else 0))
+
+
+SCAN_WORK_NAMES = ("groups_derived", "pbkdf2_launches", "line_rows")
+
+
+def scan_work(reset: bool = False) -> dict:
+    """What the scan path has launched in this process since the last reset (test hook): ESSID groups derived (per
+    multi-group launch its groups, plus 1 per dwpa_scan_pbkdf2 that launched), multi-group PBKDF2 launches of
+    dwpa_scan_run, and line rows handed to the verify kernels.  A retired line or group adds to none of them."""
+    out = (ctypes.c_uint64 * 3)()
+    load().dwpa_debug_scan_work(out, 1 if reset else 0)
+    return dict(zip(SCAN_WORK_NAMES, (int(v) for v in out)))
 
 
 def check(rc: int, what: str = "") -> int:

@@ -1764,6 +1764,10 @@ int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minl
     return 0;
 }
 
+// What the scan path has launched in this process (dwpa_debug_scan_work, a test hook): ESSID groups derived (a fully
+// cracked group costs no PBKDF2), multi-group PBKDF2 launches, and line rows handed to the verifier.
+static std::atomic<uint64_t> g_scan_groups_derived{0}, g_scan_mg_launches{0}, g_scan_line_rows{0};
+
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream) {
     if (!sc || group < 0 || group >= (int)sc->groups.size()) return DWPA_E_ARG;
     HIPCHK(hipSetDevice(sc->device));
@@ -1774,6 +1778,7 @@ int scan_pbkdf2(dwpa_scan* sc, int group, void* stream) {
     HIPCHK(launch_pbkdf2((const uint32_t*)sc->batch.mid.p, sc->batch_cap, 0, sc->batch_cap,
                          (const uint32_t*)sc->batch.counters.p, (const uint32_t*)sc->salt.p + g.salt_off, g.nsalt,
                          (uint32_t*)sc->batch.pmk.p, as_stream(stream), (uint32_t*)sc->batch.counters.p + 2));
+    g_scan_groups_derived.fetch_add(1, std::memory_order_relaxed);
     return 0;
 }
 
@@ -1793,6 +1798,7 @@ int scan_verify(dwpa_scan* sc, int group, void* stream) {
                              (const LineDev*)sc->lines.p, (const uint32_t*)sc->pool.p, (const AttDev*)sc->atts.p,
                              (HitDev*)sc->batch.hits.p, (uint32_t*)sc->batch.counters.p + 1, sc->batch.hitcap,
                              vc, as_stream(stream)));
+        g_scan_line_rows.fetch_add(e - l, std::memory_order_relaxed);
         l = e;
     }
     return 0;
@@ -1867,7 +1873,12 @@ int scan_run(dwpa_scan* sc, void* stream) {
         HIPCHK(launch_pbkdf2_mg((const uint32_t*)sc->batch.mid.p, cap, (const uint32_t*)sc->batch.counters.p,
                                 ch.ngroups, (const uint32_t*)sc->salt.p, (const uint32_t*)sc->mg_gsalt.p + 2 * ch.g0,
                                 (uint32_t*)sc->mg_pmk.p, pstride, s, (uint32_t*)sc->batch.counters.p + 2));
-        for (uint32_t c = 0; c < 4; c++)  // one launch per verify class (grid.y <= 65535 lines)
+        g_scan_groups_derived.fetch_add(ch.ngroups, std::memory_order_relaxed);
+        g_scan_mg_launches.fetch_add(1, std::memory_order_relaxed);
+        // One launch per verify class, cut at 65535 lines (CUDA's grid.y bound).  The HIP runtime does not need the
+        // cut: it takes a larger grid.y -- scan_verify passes a whole run on, the rule launches every rule -- and
+        // tests/test_gpu_retire_recall.py runs all three with 65,540 lines and 70,000 rules.
+        for (uint32_t c = 0; c < 4; c++)
             for (uint32_t l = ch.cls[c]; l < ch.cls[c + 1]; l += 65535u) {
                 const uint32_t nl = std::min<uint32_t>(65535u, ch.cls[c + 1] - l);
                 HIPCHK(launch_verify((const uint32_t*)sc->mg_pmk.p, cap, (const uint64_t*)sc->batch.ids.p,
@@ -1876,6 +1887,7 @@ int scan_run(dwpa_scan* sc, void* stream) {
                                      (const AttDev*)sc->atts.p, (HitDev*)sc->batch.hits.p,
                                      (uint32_t*)sc->batch.counters.p + 1, sc->batch.hitcap, 1u << c, s,
                                      (const uint32_t*)sc->mg_list.p, (const uint32_t*)sc->mg_poff.p, pstride));
+                g_scan_line_rows.fetch_add(nl, std::memory_order_relaxed);
             }
     }
     return 0;
@@ -1969,6 +1981,17 @@ uint32_t dwpa_debug_verify_kernels(int reset) {
 uint64_t dwpa_debug_check_hit_records(int reset) {
     return reset ? g_check_hit_records.exchange(0u, std::memory_order_relaxed)
                  : g_check_hit_records.load(std::memory_order_relaxed);
+}
+
+// And the scan path's work (scan_pbkdf2 / scan_verify / scan_run above): out[0] = ESSID groups derived, out[1] =
+// multi-group PBKDF2 launches, out[2] = line rows verified.  A retired line or group adds to none of them.
+void dwpa_debug_scan_work(uint64_t out[3], int reset) {
+    std::atomic<uint64_t>* c[3] = {&g_scan_groups_derived, &g_scan_mg_launches, &g_scan_line_rows};
+    for (int i = 0; i < 3; i++) {
+        const uint64_t v = reset ? c[i]->exchange(0u, std::memory_order_relaxed)
+                                 : c[i]->load(std::memory_order_relaxed);
+        if (out) out[i] = v;
+    }
 }
 
 int dwpa_init(const dwpa_config* cfg) {
