@@ -199,6 +199,7 @@ SIGNATURES = {
     "dwpa_debug_verify_kernels": ([ctypes.c_int], ctypes.c_uint32),  # test hook, not in include/dwpa22000.h
     "dwpa_debug_check_hit_records": ([ctypes.c_int], ctypes.c_uint64),  # test hook, not in include/dwpa22000.h
     "dwpa_debug_scan_work": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_int], None),  # test hook, not in the header
+    "dwpa_debug_crack_loads": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_int], None),  # test hook, not in the header
 }
 
 # Bit i of dwpa_debug_pbkdf2_kernels' mask (csrc/kernels.hpp Pbkdf2Kernel): the hipcc-scheduled kernels of kernels.hip,
@@ -265,6 +266,18 @@ def scan_work(reset: bool = False) -> dict:
     out = (ctypes.c_uint64 * 3)()
     load().dwpa_debug_scan_work(out, 1 if reset else 0)
     return dict(zip(SCAN_WORK_NAMES, (int(v) for v in out)))
+
+
+CRACK_LOAD_NAMES = ("loads", "overflowed", "empty", "scanned")
+
+
+def crack_loads(reset: bool = False) -> dict:
+    """What the crack loop's load sizing has issued in this process since the last reset (test hook), over the
+    dictionary, rules, hybrid and combinator runs: device loads, loads that overflowed the batch and were repeated
+    with fewer words, loads that kept nothing (no scan), and loads scanned.  loads = overflowed + empty + scanned."""
+    out = (ctypes.c_uint64 * 4)()
+    load().dwpa_debug_crack_loads(out, 1 if reset else 0)
+    return dict(zip(CRACK_LOAD_NAMES, (int(v) for v in out)))
 
 
 def check(rc: int, what: str = "") -> int:

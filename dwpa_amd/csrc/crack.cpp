@@ -123,6 +123,11 @@ static int read_amplifier(const char* path, CombiSpec* cb) {
     return 0;
 }
 
+// What the sizing loops of scan_shard and scan_shard_combi have issued in this process (dwpa_debug_crack_loads, a test
+// hook): device loads, loads that overflowed the batch and were repeated, loads that kept nothing, loads scanned.
+static std::atomic<uint64_t> g_loads_issued{0}, g_loads_overflowed{0}, g_loads_empty{0}, g_loads_scanned{0};
+static void count_load(std::atomic<uint64_t>& c) { c.fetch_add(1, std::memory_order_relaxed); }
+
 struct CrackShared {
     std::mutex mu;
     std::vector<uint8_t> cracked;         // per input line (1: cracked, or never usable)
@@ -253,6 +258,44 @@ static int scan_shard_wide(DevWork& w, CrackShared& sh, const Chunk& c, size_t b
     return 0;
 }
 
+// More rules than the batch: one word's results no longer fit a load, so the sizing loop has nothing to size (it
+// gave up with DWPA_E_OVERFLOW, and past 16 batches of rules rules_load refused the load).  As scan_shard_wide does
+// for a mask: one word x consecutive rule ranges of a batch each.  A word the rule engine refuses (empty, or longer
+// than its 256 bytes) costs no launch, a range that keeps nothing no scan.  The ids stay word * nrules + rule.
+static int scan_shard_rules_wide(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, size_t e, const RuleSet& rules,
+                                 int slot) {
+    const uint32_t cap = scan_batch_cap(w.scan);
+    const uint64_t nrules = rules.size();
+    std::vector<HitDev> hits;
+    for (size_t wi = b; wi < e; wi++) {
+        const uint64_t L = c.off[wi + 1] - c.off[wi];
+        if (L < 1 || L > (uint64_t)RP_PASSWORD_SIZE) continue;
+        for (uint64_t rf = 0; rf < nrules && !sh.stop.load(std::memory_order_relaxed); rf += cap) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(cap, nrules - rf);
+            int r;
+            if ((r = rules_load(w.scan, &w.rules, (const uint64_t*)w.off[slot].p, (const uint8_t*)w.bytes[slot].p,
+                                wi - b, 1, w.stream, false, (uint32_t)rf, n)) < 0)
+                return r;
+            uint32_t raw = 0;
+            if ((r = scan_counter_raw(w.scan, w.stream, &raw)) < 0) return r;
+            if (raw > n) return DWPA_E_OVERFLOW;  // cannot happen: one word x n <= batch rules
+            if (raw == 0) continue;
+            sync_retired(w, sh);
+            if ((r = scan_run(w.scan, w.stream)) < 0) return r;
+            w.cands += raw;
+            if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
+            if (hits.empty()) continue;
+            report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+                if (cand / nrules != wi - b) return false;
+                plain->assign(c.bytes.data() + c.off[wi], (size_t)L);
+                return rules.apply_host((size_t)(cand % nrules), *plain, plain);
+            });
+        }
+        if (sh.stop.load(std::memory_order_relaxed)) break;
+    }
+    return 0;
+}
+
 // The amplifier list of a combinator run, once per worker, with the 64 bytes of padding stage_shard gives.
 static int upload_amplifier(DevWork& w, const CombiSpec& cb) {
     if (hipSetDevice(w.device) != hipSuccess) return DWPA_E_HIP;
@@ -324,7 +367,9 @@ static int scan_shard_combi(DevWork& w, CrackShared& sh, const Chunk& c, size_t 
             if (kept + k > cap) break;
             kept += k;
         }
+        count_load(g_loads_issued);
         if (kept == 0) {
+            count_load(g_loads_empty);
             wb += nw;
             continue;
         }
@@ -340,6 +385,7 @@ static int scan_shard_combi(DevWork& w, CrackShared& sh, const Chunk& c, size_t 
         }
         sync_retired(w, sh);
         if ((r = scan_run(w.scan, w.stream)) < 0) return r;
+        count_load(g_loads_scanned);
         const size_t first = b + wb;
         wb += nw;
         w.cands += kept;
@@ -366,6 +412,7 @@ static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, siz
     const uint32_t cap = scan_batch_cap(w.scan);
     const size_t words = e - b;
     if (hy && hy->mask->keyspace > cap) return scan_shard_wide(w, sh, c, b, e, *hy, slot);
+    if (!hy && rules && rules->size() > cap) return scan_shard_rules_wide(w, sh, c, b, e, *rules, slot);
     // a hybrid run's amplifier is its mask: K candidates per word where a rules run has nrules
     const uint64_t nrules = hy ? hy->mask->keyspace : rules ? rules->size() : 1;
     // candidate id = word * nrules + rule; batches walk the candidate space in order.  Every PBKDF2 lane runs the
@@ -390,21 +437,25 @@ static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, siz
             r = scan_load_dict(w.scan, (const uint64_t*)woff.p, (const uint8_t*)wbytes.p, wb, nw, 8, 63, w.stream,
                                true);
         if (r < 0) return r;
+        count_load(g_loads_issued);
         uint32_t raw = 0;
         if ((r = scan_counter_raw(w.scan, w.stream, &raw)) < 0) return r;
         const double seen = (double)raw / ((double)nw * nrules);
         if (raw > cap) {  // overflow: nothing derived yet, retry these words in a smaller batch
             if (nw == 1) return DWPA_E_OVERFLOW;
+            count_load(g_loads_overflowed);
             keep = std::max(seen, keep * 1.05);
             continue;
         }
         if (raw > 0) keep = std::min(1.0, std::max(0.01, seen));
         if (raw == 0) {
+            count_load(g_loads_empty);
             wb += nw;
             continue;
         }
         sync_retired(w, sh);
         if ((r = scan_run(w.scan, w.stream)) < 0) return r;  // all ESSID groups, grouped per launch
+        count_load(g_loads_scanned);
         wb += nw;
         w.cands += raw;
         std::vector<HitDev> hits;
@@ -931,6 +982,18 @@ int dwpa_crack_files(const char* hash_file, const char* const* dicts, size_t ndi
     return dwpa::guarded([&]() -> int {
         return dwpa::crack_impl(hash_file, dicts, ndicts, rules_file, nonce_error_corrections, out_file, cfg, nullptr);
     }, DWPA_RC_ERROR, DWPA_RC_ERROR);
+}
+
+// Test hook (outside include/dwpa22000.h and the ABI version): out[0..3] = loads issued, overflowed and repeated, kept
+// nothing, scanned, by the sizing loops of the dictionary, rules, hybrid and combinator runs of this process.
+void dwpa_debug_crack_loads(uint64_t out[4], int reset) {
+    std::atomic<uint64_t>* c[4] = {&dwpa::g_loads_issued, &dwpa::g_loads_overflowed, &dwpa::g_loads_empty,
+                                   &dwpa::g_loads_scanned};
+    for (int i = 0; i < 4; i++) {
+        const uint64_t v = reset ? c[i]->exchange(0u, std::memory_order_relaxed)
+                                 : c[i]->load(std::memory_order_relaxed);
+        if (out) out[i] = v;
+    }
 }
 
 int dwpa_crack_last_stats(dwpa_crack_stats* out) {

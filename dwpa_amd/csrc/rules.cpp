@@ -221,13 +221,21 @@ int rules_upload(int device, const RuleSet& rs, DevRules* out) {
 }
 
 int rules_load(dwpa_scan* scan, const DevRules* r, const uint64_t* off, const uint8_t* bytes, uint64_t first,
-               uint32_t nwords, hipStream_t s, bool fill) {
-    if (!scan || !r || (uint64_t)nwords * r->nrules > (fill ? 16ull : 1ull) * scan_batch_cap(scan)) return DWPA_E_ARG;
+               uint32_t nwords, hipStream_t s, bool fill, uint32_t rule0, uint32_t nrange) {
+    if (!scan || !r) return DWPA_E_ARG;
+    if (nrange == 0) {  // every rule
+        rule0 = 0;
+        nrange = r->nrules;
+    }
+    if (rule0 > r->nrules || nrange > r->nrules - rule0 ||
+        (uint64_t)nwords * nrange > (fill ? 16ull : 1ull) * scan_batch_cap(scan))
+        return DWPA_E_ARG;
     Batch& b = scan_batch_ref(scan);
     if (hipSetDevice(r->device) != hipSuccess) return DWPA_E_HIP;
     if (hipMemsetAsync(b.counters.p, 0, 4, s) != hipSuccess) return DWPA_E_HIP;
-    if (launch_rules_prep(off, bytes, first, nwords, (const uint32_t*)r->offs, (const uint32_t*)r->code, r->nrules, 8,
-                          63, (uint32_t*)b.mid.p, (uint64_t*)b.ids.p, (uint32_t*)b.counters.p, b.cap, s) != hipSuccess)
+    if (launch_rules_prep(off, bytes, first, nwords, (const uint32_t*)r->offs, (const uint32_t*)r->code, r->nrules,
+                          rule0, nrange, 8, 63, (uint32_t*)b.mid.p, (uint64_t*)b.ids.p, (uint32_t*)b.counters.p, b.cap,
+                          s) != hipSuccess)
         return DWPA_E_HIP;
     return 0;
 }

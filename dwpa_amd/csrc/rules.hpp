@@ -78,8 +78,10 @@ int rules_upload(int device, const RuleSet& rs, DevRules* out);
 void rules_release(DevRules* r);
 // Stage 1 for word x rule candidates: words [first, first+nwords) of an HBM dictionary, every rule; candidates
 // outside 8..63 bytes (or rejected by a rule) are dropped; candidate id = word * nrules + rule.
+// nrange != 0: only rules [rule0, rule0 + nrange) of the set (a rule set wider than the batch goes range by range);
+// the ids are the same.  The words x the rules of the load must fit the batch (16 batches with fill).
 int rules_load(dwpa_scan* scan, const DevRules* r, const uint64_t* off, const uint8_t* bytes, uint64_t first,
-               uint32_t nwords, hipStream_t s, bool fill = false);
+               uint32_t nwords, hipStream_t s, bool fill = false, uint32_t rule0 = 0, uint32_t nrange = 0);
 
 // out: nwords x nrules 256-byte slots, out_len their lengths (0xFFFFFFFF = rejected); text_len (nullable): each
 // candidate's bytes in --stdout text (raw + '\n', or $HEX[..] + '\n' when it holds '\n' / '\r'; 0 = rejected).
@@ -95,8 +97,8 @@ hipError_t launch_text_pack(const uint8_t* out, const uint32_t* out_len, const u
                             uint32_t* bsum, uint32_t* bcnt, uint32_t* tot, uint8_t* text, uint64_t cap,
                             hipStream_t s);
 hipError_t launch_rules_prep(const uint64_t* off, const uint8_t* bytes, uint64_t first, uint32_t nwords,
-                             const uint32_t* roffs, const uint32_t* rcode, uint32_t nrules, uint32_t minlen,
-                             uint32_t maxlen, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
-                             hipStream_t s);
+                             const uint32_t* roffs, const uint32_t* rcode, uint32_t nrules, uint32_t rule0,
+                             uint32_t nrange, uint32_t minlen, uint32_t maxlen, uint32_t* mid, uint64_t* ids,
+                             uint32_t* counter, uint32_t cap, hipStream_t s);
 
 }  // namespace dwpa

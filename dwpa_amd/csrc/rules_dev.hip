@@ -31,12 +31,12 @@ __device__ __forceinline__ int load_word(const uint64_t* __restrict__ off, const
 
 __global__ __launch_bounds__(256) void k_rules_prep(const uint64_t* __restrict__ off, const uint8_t* __restrict__ bytes,
                                                     uint64_t first, uint32_t nwords, const uint32_t* __restrict__ roffs,
-                                                    const uint32_t* __restrict__ rcode, uint32_t nrules, uint32_t minlen,
-                                                    uint32_t maxlen, uint32_t* __restrict__ mid,
+                                                    const uint32_t* __restrict__ rcode, uint32_t nrules, uint32_t rule0,
+                                                    uint32_t minlen, uint32_t maxlen, uint32_t* __restrict__ mid,
                                                     uint64_t* __restrict__ ids, uint32_t* __restrict__ counter,
                                                     uint32_t cap) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t r = blockIdx.y;
+    const uint32_t r = rule0 + blockIdx.y;  // the launch covers rules [rule0, rule0 + gridDim.y) of the nrules
     uint8_t w[RP_PASSWORD_SIZE + 4], mem[RP_PASSWORD_SIZE + 4];
     int len = -1;
     if (i < nwords) {
@@ -208,12 +208,13 @@ __global__ __launch_bounds__(256) void k_text_pack(const uint8_t* __restrict__ o
 }
 
 hipError_t launch_rules_prep(const uint64_t* off, const uint8_t* bytes, uint64_t first, uint32_t nwords,
-                             const uint32_t* roffs, const uint32_t* rcode, uint32_t nrules, uint32_t minlen,
-                             uint32_t maxlen, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
-                             hipStream_t s) {
-    if (nwords == 0 || nrules == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rules_prep, dim3((nwords + 255) / 256, nrules), dim3(256), 0, s, off, bytes, first, nwords,
-                       roffs, rcode, nrules, minlen, maxlen, mid, ids, counter, cap);
+                             const uint32_t* roffs, const uint32_t* rcode, uint32_t nrules, uint32_t rule0,
+                             uint32_t nrange, uint32_t minlen, uint32_t maxlen, uint32_t* mid, uint64_t* ids,
+                             uint32_t* counter, uint32_t cap, hipStream_t s) {
+    if (nwords == 0 || nrange == 0) return hipSuccess;
+    if (rule0 > nrules || nrange > nrules - rule0) return hipErrorInvalidValue;  // roffs holds nrules + 1 offsets
+    hipLaunchKernelGGL(k_rules_prep, dim3((nwords + 255) / 256, nrange), dim3(256), 0, s, off, bytes, first, nwords,
+                       roffs, rcode, nrules, rule0, minlen, maxlen, mid, ids, counter, cap);
     return hipGetLastError();
 }
 

@@ -103,6 +103,28 @@ def test_debug_scan_work_hook():
     assert r.stdout.strip() == " ".join([zero] * 3)
 
 
+def test_debug_crack_loads_hook():
+    """dwpa_debug_crack_loads (the test hook tests/test_gpu_fill_recall.py reads the crack loop's loads issued,
+    overflowed, empty and scanned from): exported, outside the public header, the PHP cdef and the ABI version, zero
+    in a process that has launched nothing, and `reset` returns the counters it clears."""
+    import subprocess
+    import sys
+    lib = L.load()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    php = open(os.path.join(root, "php", "dwpa22000.php")).read()
+    hook = "dwpa_debug_crack_loads"
+    assert hasattr(lib, hook)
+    assert hook not in declared_symbols() and hook not in open(L.HEADER).read() and hook not in php
+    assert lib.dwpa_abi_version() == 4
+    assert L.CRACK_LOAD_NAMES == ("loads", "overflowed", "empty", "scanned")
+    child = ("import sys; sys.path.insert(0, sys.argv[1]); from dwpa_amd import _lib as L; lib = L.load(); "
+             "print(L.crack_loads(), L.crack_loads(reset=True), L.crack_loads()); lib.dwpa_debug_crack_loads(None, 1)")
+    r = subprocess.run([sys.executable, "-c", child, root], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    zero = str(dict.fromkeys(L.CRACK_LOAD_NAMES, 0))
+    assert r.stdout.strip() == " ".join([zero] * 3)
+
+
 def test_hc_unhex_matches_oracle():
     import dwpa_amd
     for k in [b"$HEX[414243]", b"$HEX[]", b"$HEX[41424]", b"$HEX[41zz]", b"$HEX[4142]x", b"plain", b"$HEX[00ff]",

@@ -21,7 +21,8 @@ Batch& scan_batch_ref(dwpa_scan*) { not_here(); }
 int scan_device(const dwpa_scan*) { not_here(); }
 int engine_init() { not_here(); }
 hipError_t launch_rules_prep(const uint64_t*, const uint8_t*, uint64_t, uint32_t, const uint32_t*, const uint32_t*,
-                             uint32_t, uint32_t, uint32_t, uint32_t*, uint64_t*, uint32_t*, uint32_t, hipStream_t) {
+                             uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, uint64_t*, uint32_t*, uint32_t,
+                             hipStream_t) {
     not_here();
 }
 hipError_t launch_rules_expand(const uint64_t*, const uint8_t*, uint32_t, const uint32_t*, const uint32_t*, uint32_t,
