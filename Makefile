@@ -8,8 +8,8 @@ LIB := dwpa_amd/lib/libdwpa22000.so
 HDRS := $(wildcard $(SRC)/*.hpp) include/dwpa22000.h
 OBJS := $(OBJ)/kernels.o $(OBJ)/rules_dev.o $(OBJ)/engine.o $(OBJ)/m22000_host.o $(OBJ)/crack.o $(OBJ)/rules.o \
         $(OBJ)/pbkdf2_module.o $(OBJ)/pbkdf2_hsaco.o $(OBJ)/host_crypto.o $(OBJ)/host_check.o \
-        $(OBJ)/mask.o $(OBJ)/mask_dev.o $(OBJ)/crack_mask.o $(OBJ)/hybrid_dev.o \
-        $(OBJ)/combi_dev.o $(OBJ)/chain.o $(OBJ)/chain_dev.o $(OBJ)/crack_chain.o
+        $(OBJ)/mask.o $(OBJ)/mask_dev.o $(OBJ)/crack_common.o $(OBJ)/hybrid_dev.o \
+        $(OBJ)/combi_dev.o $(OBJ)/chain.o $(OBJ)/chain_dev.o $(OBJ)/crack_range.o
 LLVM := /opt/rocm/lib/llvm/bin
 ISSUE_RULE ?= sched=1:alt:orig:asmnop,before_half
 # 1: the two work-queue PBKDF2 kernels keep their cold words in LDS (pbkdf2_dev.hpp pbkdf2_lane_lds); 0: the plain lane
@@ -85,7 +85,7 @@ clean:
 tools: tools/bin/valu_peak tools/bin/pbkdf2_lab tools/bin/valu_lat tools/bin/valu_peak64 tools/bin/inflate_bench \
        tools/bin/inflate_check tools/bin/item_queue_check tools/bin/rules_fuzz_asan tools/bin/clock_idle \
        tools/bin/inflate_check_tsan tools/bin/tail_placement tools/bin/parse_fuzz_asan tools/bin/host_check_fuzz_asan tools/bin/host_pbkdf2_paths tools/bin/vgpr_bank \
-       tools/bin/mask_fuzz_asan tools/bin/chain_fuzz_asan
+       tools/bin/mask_fuzz_asan tools/bin/chain_fuzz_asan tools/bin/range_cursor_check
 
 tools/bin/valu_lat: tools/valu_lat.hip
 	@mkdir -p tools/bin
@@ -171,3 +171,8 @@ tools/bin/inflate_check_tsan: tools/inflate_check.cpp $(SRC)/inflate.hpp $(SRC)/
 	@mkdir -p tools/bin
 	g++ -O1 -g -std=c++17 -Wall -I$(SRC) -fsanitize=thread -DDWPA_PINFLATE_LOAD_STEP=16384 -o $@ tools/inflate_check.cpp \
 	    -lz -lpthread
+
+# the range attacks' shared cursor (crack_cursor.hpp) with concurrent takers under ThreadSanitizer
+tools/bin/range_cursor_check: tools/range_cursor_check.cpp $(SRC)/crack_cursor.hpp
+	@mkdir -p tools/bin
+	g++ -O1 -g -std=c++17 -Wall -I$(SRC) -fsanitize=thread -o $@ tools/range_cursor_check.cpp -lpthread

@@ -11,6 +11,8 @@
 // would: each word is joined with the mask's candidates on the GPU (hybrid_dev.hip).
 // dwpa_crack_combinator() (hashcat -a 1) is the same call again with a second word list as the amplifier: it lies
 // whole in device memory and every streamed word is joined with its words on the GPU (combi_dev.hip).
+// The call frame -- checks, hash file, outfile, scan workers, retirement, hit reporting, statistics -- is the one all
+// crack calls share (crack_common.hpp); what is here is the dictionary feed and the sizing of the loads.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -29,6 +31,7 @@
 #include <vector>
 
 #include "dwpa22000.h"
+#include "crack_common.hpp"
 #include "engine.hpp"
 #include "m22000_host.hpp"
 #include "dict_reader.hpp"
@@ -48,18 +51,14 @@ struct HybridSpec {
 // dwpa_crack_combinator: one of the two lists is the amplifier of every word of the other (the base, which is
 // streamed as a dictionary run streams its words).  The amplifier is read whole into host memory once: it is uploaded
 // once per worker and kept here to rebuild a hit's PSK.  valid = false: the side was refused.
-struct CombiSpec {
+struct CombiSpec : HostList {      // the amplifier list, A words
     int side = DWPA_COMBI_AMP_RIGHT;
     bool valid = false;
-    std::vector<uint64_t> off{0};  // A + 1 offsets into bytes
-    std::string bytes;
-    int status = DWPA_DICT_OK;     // of the amplifier list (DWPA_DICT_DAMAGED: read up to the damage)
     uint64_t below[65] = {};       // below[k]: amplifier words shorter than k bytes, k <= 64
     // A > batch: range_below[r * 65 + k] = amplifier words before index r * range that are shorter than k bytes
     std::vector<uint32_t> range_below;
     uint64_t range = 0;
 
-    uint64_t words() const { return off.size() - 1; }
     size_t base_index() const { return side == DWPA_COMBI_AMP_RIGHT ? 0 : 1; }  // of {left, right}
     // The amplifier words that a base word of L bytes keeps have lo..hi bytes (8 <= L + R <= 63); false: none can.
     static bool window(uint64_t L, uint32_t* lo, uint32_t* hi) {
@@ -104,64 +103,23 @@ struct CombiSpec {
     }
 };
 
-// The amplifier list through the dictionary reader (plain or gzip, CRLF, $HEX[]), whole.  DWPA_E_IO: a read error;
-// DWPA_E_OVERFLOW: above the limit.
-static int read_amplifier(const char* path, CombiSpec* cb) {
-    DictReader rd({std::string(path)});
-    Chunk c;
-    bool err = false;
-    while (rd.next(c, (size_t)1 << 20, (size_t)64 << 20, err)) {
-        const uint64_t at = cb->bytes.size();
-        cb->bytes += c.bytes;
-        for (size_t i = 1; i < c.off.size(); i++) cb->off.push_back(at + c.off[i]);
-        if (cb->words() > UINT32_MAX || cb->bytes.size() + cb->off.size() * 8 > DWPA_COMBI_AMP_MAX_BYTES)
-            return DWPA_E_OVERFLOW;
-    }
-    if (err) return DWPA_E_IO;
-    if (rd.damaged()) cb->status = DWPA_DICT_DAMAGED;
-    cb->count_lengths();
-    return 0;
-}
-
 // What the sizing loops of scan_shard and scan_shard_combi have issued in this process (dwpa_debug_crack_loads, a test
 // hook): device loads, loads that overflowed the batch and were repeated, loads that kept nothing, loads scanned.
 static std::atomic<uint64_t> g_loads_issued{0}, g_loads_overflowed{0}, g_loads_empty{0}, g_loads_scanned{0};
 static void count_load(std::atomic<uint64_t>& c) { c.fetch_add(1, std::memory_order_relaxed); }
 
-struct CrackShared {
-    std::mutex mu;
-    std::vector<uint8_t> cracked;         // per input line (1: cracked, or never usable)
-    std::vector<ParsedLine> parsed;
-    FILE* out = nullptr;
-    size_t valid = 0, ncracked = 0;
-    std::atomic<uint32_t> version{0};     // bumped for every newly cracked line: workers re-sync their scans
-    std::atomic<bool> stop{false};        // every usable line cracked, or an error
-    std::atomic<int> error{0};
-};
-
-std::string outfile_record(const ParsedLine& p, const std::string& psk) {
-    const std::string& target = p.kind == LINE_PMKID ? p.pmkid : p.keymic;
-    return hex_lower(target.substr(0, 16)) + ":" + hex_lower(p.mac_ap) + ":" + hex_lower(p.mac_sta) + ":" +
-           hashcat_plain(p.essid) + ":" + hashcat_plain(psk) + "\n";
-}
-
 // One shard worker (one per device, or DWPA_CRACK_SHARDS_PER_DEVICE per device).  Its stager thread uploads the
 // next item into the free one of two buffer slots on the `up` stream while its scanner thread scans the other.
-struct DevWork {
-    int device = 0;
-    dwpa_scan* scan = nullptr;
+struct DevWork : ScanWorker {
     DevRules rules;
     DevBuf off[2], bytes[2];
     DevBuf amp_off, amp_bytes;      // dwpa_crack_combinator: the amplifier list, uploaded once
     std::vector<uint64_t> hoff[2];  // host staging of the rebased offsets (alive until the upload completes)
-    hipStream_t stream = nullptr, up = nullptr;
+    hipStream_t up = nullptr;
     hipEvent_t staged[2] = {nullptr, nullptr};
     double keep = 1.0;              // surviving candidates per (word x rule), carried from item to item
-    uint32_t seen_version = 0;      // sh.version this scan's retired lines reflect
-    size_t items = 0, words = 0;    // statistics (DWPA_TRACE, dwpa_crack_last_stats)
-    uint64_t cands = 0;             // candidates loaded inside the 8..63 filter (after rules)
+    size_t words = 0;               // of the items scanned (DWPA_TRACE, dwpa_crack_last_stats)
     double wait_s = 0;              // scanner time spent waiting for a staged item
-    double scan_s = 0;              // scanner time spent scanning items
     // stager -> scanner hand-over
     std::mutex mu;
     std::condition_variable cv;
@@ -189,38 +147,6 @@ static int stage_shard(DevWork& w, const Chunk& c, size_t b, size_t e, int slot)
     return 0;
 }
 
-// Retire on w's scan every line cracked anywhere so far (hashcat reports each hash once).
-static void sync_retired(DevWork& w, CrackShared& sh) {
-    const uint32_t v = sh.version.load(std::memory_order_acquire);
-    if (v == w.seen_version) return;
-    std::lock_guard<std::mutex> lk(sh.mu);
-    for (size_t i = 0; i < sh.cracked.size(); i++)
-        if (sh.cracked[i]) scan_mark_cracked(w.scan, (uint32_t)i);
-    w.seen_version = v;
-}
-
-// The first hit of each line (lowest candidate id first) is written to the outfile once and the line retired;
-// plain_of rebuilds a candidate's PSK on the host from its id.
-template <class F>
-static void report_hits(DevWork& w, CrackShared& sh, std::vector<HitDev>& hits, F&& plain_of) {
-    std::sort(hits.begin(), hits.end(), [](const HitDev& x, const HitDev& y) { return x.cand < y.cand; });
-    std::lock_guard<std::mutex> lk(sh.mu);
-    std::string plain;
-    for (const HitDev& h : hits) {
-        dwpa_hit ph;
-        hit_to_public(w.scan, h, ph);
-        if (sh.cracked[ph.line]) continue;
-        if (!plain_of(h.cand, &plain)) continue;
-        sh.cracked[ph.line] = 1;
-        sh.ncracked++;
-        sh.version.fetch_add(1, std::memory_order_acq_rel);
-        const std::string rec = outfile_record(sh.parsed[ph.line], plain);
-        fwrite(rec.data(), 1, rec.size(), sh.out);
-        fflush(sh.out);
-    }
-    if (sh.ncracked == sh.valid) sh.stop = true;
-}
-
 // A mask wider than the batch: one word x consecutive mask ranges of a batch each.  Whether a word survives the
 // 8..63 filter follows from its length alone, so a dropped word costs no launch.  Each word is loaded as word 0 of
 // the offsets from its own entry on: the ids are then the mask indices, whatever words * K would come to.
@@ -239,12 +165,7 @@ static int scan_shard_wide(DevWork& w, CrackShared& sh, const Chunk& c, size_t b
             if ((r = scan_load_hybrid(w.scan, (const uint64_t*)w.off[slot].p + (wi - b), (const uint8_t*)w.bytes[slot].p,
                                       0, 1, mf, n, hy.mode, 8, 63, w.stream)) < 0)
                 return r;
-            sync_retired(w, sh);
-            if ((r = scan_run(w.scan, w.stream)) < 0) return r;
-            w.cands += n;
-            if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
-            if (hits.empty()) continue;
-            report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+            r = scan_step(w, sh, hits, [&](uint64_t cand, std::string* plain) {
                 if (cand >= K) return false;
                 uint8_t m[64];
                 mask_candidate(*hy.mask, cand, m);
@@ -252,6 +173,8 @@ static int scan_shard_wide(DevWork& w, CrackShared& sh, const Chunk& c, size_t b
                 *plain = hy.mode == DWPA_HYBRID_WORD_MASK ? word + ms : ms + word;
                 return true;
             });
+            if (r < 0) return r;
+            w.cands += n;
         }
         if (sh.stop.load(std::memory_order_relaxed)) break;
     }
@@ -280,30 +203,16 @@ static int scan_shard_rules_wide(DevWork& w, CrackShared& sh, const Chunk& c, si
             if ((r = scan_counter_raw(w.scan, w.stream, &raw)) < 0) return r;
             if (raw > n) return DWPA_E_OVERFLOW;  // cannot happen: one word x n <= batch rules
             if (raw == 0) continue;
-            sync_retired(w, sh);
-            if ((r = scan_run(w.scan, w.stream)) < 0) return r;
-            w.cands += raw;
-            if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
-            if (hits.empty()) continue;
-            report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+            r = scan_step(w, sh, hits, [&](uint64_t cand, std::string* plain) {
                 if (cand / nrules != wi - b) return false;
                 plain->assign(c.bytes.data() + c.off[wi], (size_t)L);
                 return rules.apply_host((size_t)(cand % nrules), *plain, plain);
             });
+            if (r < 0) return r;
+            w.cands += raw;
         }
         if (sh.stop.load(std::memory_order_relaxed)) break;
     }
-    return 0;
-}
-
-// The amplifier list of a combinator run, once per worker, with the 64 bytes of padding stage_shard gives.
-static int upload_amplifier(DevWork& w, const CombiSpec& cb) {
-    if (hipSetDevice(w.device) != hipSuccess) return DWPA_E_HIP;
-    if (w.amp_off.ensure(cb.off.size() * 8) || w.amp_bytes.ensure(cb.bytes.size() + 64)) return DWPA_E_NOMEM;
-    if (hipMemcpy(w.amp_off.p, cb.off.data(), cb.off.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
-        (!cb.bytes.empty() &&
-         hipMemcpy(w.amp_bytes.p, cb.bytes.data(), cb.bytes.size(), hipMemcpyHostToDevice) != hipSuccess))
-        return DWPA_E_HIP;
     return 0;
 }
 
@@ -343,16 +252,13 @@ static int scan_shard_combi(DevWork& w, CrackShared& sh, const Chunk& c, size_t 
                 if ((r = scan_load_combinator(w.scan, boff + (wi - b), bbytes, 0, 1, aoff, abytes, A, af, n, cb.side, 8,
                                               63, w.stream)) < 0)
                     return r;
-                sync_retired(w, sh);
-                if ((r = scan_run(w.scan, w.stream)) < 0) return r;
-                w.cands += kept;
-                if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
-                if (hits.empty()) continue;
-                report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+                r = scan_step(w, sh, hits, [&](uint64_t cand, std::string* plain) {
                     if (cand >= A) return false;
                     join(wi, cand, plain);
                     return true;
                 });
+                if (r < 0) return r;
+                w.cands += kept;
             }
         }
         return 0;
@@ -383,20 +289,16 @@ static int scan_shard_combi(DevWork& w, CrackShared& sh, const Chunk& c, size_t 
                     (unsigned long long)kept);
             return DWPA_E_OVERFLOW;
         }
-        sync_retired(w, sh);
-        if ((r = scan_run(w.scan, w.stream)) < 0) return r;
-        count_load(g_loads_scanned);
-        const size_t first = b + wb;
-        wb += nw;
-        w.cands += kept;
-        if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
-        if (hits.empty()) continue;
-        report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
-            const uint64_t word = cand / A - (first - b), ai = cand % A;
+        r = scan_step(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+            const uint64_t word = cand / A - wb, ai = cand % A;
             if (word >= nw) return false;
-            join(first + word, ai, plain);
+            join(b + wb + word, ai, plain);
             return true;
         });
+        if (r < 0) return r;
+        count_load(g_loads_scanned);
+        wb += nw;
+        w.cands += kept;
     }
     return 0;
 }
@@ -421,6 +323,7 @@ static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, siz
     // 99.5 % of the batch.  A load that overflows the batch (the compaction drops and counts the excess) is
     // repeated with fewer words before anything is derived.
     double& keep = w.keep;
+    std::vector<HitDev> hits;
     for (size_t wb = 0; wb < words && !sh.stop.load(std::memory_order_relaxed);) {
         // keep == 1 (nothing filtered so far): exactly one batch of candidates, which cannot overflow
         const double want = (keep >= 1.0 ? 1.0 : 0.995) * cap / ((double)nrules * keep);
@@ -453,15 +356,7 @@ static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, siz
             wb += nw;
             continue;
         }
-        sync_retired(w, sh);
-        if ((r = scan_run(w.scan, w.stream)) < 0) return r;  // all ESSID groups, grouped per launch
-        count_load(g_loads_scanned);
-        wb += nw;
-        w.cands += raw;
-        std::vector<HitDev> hits;
-        if ((r = scan_hits_raw(w.scan, hits, w.stream)) < 0) return r;
-        if (hits.empty()) continue;
-        report_hits(w, sh, hits, [&](uint64_t cand, std::string* plain) {
+        r = scan_step(w, sh, hits, [&](uint64_t cand, std::string* plain) {
             const uint64_t word = cand / nrules, rule = cand % nrules;
             plain->assign(c.bytes.data() + c.off[b + word], c.off[b + word + 1] - c.off[b + word]);
             if (hy) {
@@ -473,47 +368,12 @@ static int scan_shard(DevWork& w, CrackShared& sh, const Chunk& c, size_t b, siz
             }
             return !rules || rules->apply_host((size_t)rule, *plain, plain);  // false cannot happen: the GPU kept it
         });
+        if (r < 0) return r;
+        count_load(g_loads_scanned);
+        wb += nw;
+        w.cands += raw;
     }
     return 0;
-}
-
-// DWPA_CRACK_SHARDS_PER_DEVICE=k runs k shard workers per selected device (default 1).  On a one-GPU box k = 2
-// rehearses the multi-device path -- per-worker queues, shard scans and cross-worker line retirement -- that a
-// volunteer's 8-GPU node runs (hashcat uses every device, help_crack.py:773).
-size_t crack_shards_per_device() {
-    const char* e = getenv("DWPA_CRACK_SHARDS_PER_DEVICE");
-    const long k = e ? strtol(e, nullptr, 10) : 1;
-    return (size_t)std::min<long>(8, std::max<long>(1, k));
-}
-
-// dwpa_crack_last_stats / dwpa_crack_worker_stats: the calling thread's last crack call
-static thread_local dwpa_crack_stats g_last_stats;
-static thread_local std::vector<dwpa_crack_worker> g_last_workers;
-static thread_local bool g_have_stats = false;
-
-void crack_publish_stats(const dwpa_crack_stats& st, const std::vector<dwpa_crack_worker>& workers) {
-    g_last_stats = st;
-    g_last_workers = workers;
-    g_have_stats = true;
-}
-
-// One m22000 line per line (LF or CRLF), empty lines dropped.
-bool read_hash_file(const char* path, std::vector<std::string>& lines) {
-    FILE* f = fopen(path, "rb");
-    if (!f) return false;
-    std::string cur;
-    int ch;
-    while ((ch = fgetc(f)) != EOF) {
-        if (ch == '\n') {
-            if (!cur.empty() && cur.back() == '\r') cur.pop_back();
-            if (!cur.empty()) lines.push_back(cur);
-            cur.clear();
-        } else cur.push_back((char)ch);
-    }
-    if (!cur.empty() && cur.back() == '\r') cur.pop_back();
-    if (!cur.empty()) lines.push_back(cur);
-    fclose(f);
-    return true;
 }
 
 static bool trace_on() {
@@ -524,18 +384,11 @@ static bool trace_on() {
 static int crack_impl(const char* hash_file, const char* const* dicts, size_t ndicts, const char* rules_file, int nec,
                       const char* out_file, const dwpa_config* cfg, int32_t* dict_status,
                       const HybridSpec* hy = nullptr, CombiSpec* cb = nullptr) {
-    const auto t_call = std::chrono::steady_clock::now();
-    g_last_stats = dwpa_crack_stats{};  // an early return reports zeros, never the previous call
-    g_last_workers.clear();
-    g_have_stats = true;
+    CrackCall call;
     if (dict_status)
         for (size_t i = 0; i < ndicts; i++) dict_status[i] = DWPA_DICT_OK;
     if (!hash_file || !out_file || (!dicts && ndicts)) return DWPA_RC_ERROR;
-    if (cfg && cfg->struct_size && cfg->struct_size < offsetof(dwpa_config, batch)) return DWPA_RC_ERROR;
-    if (nec > DWPA_NC_MAX) {
-        fprintf(stderr, "[dwpa] --nonce-error-corrections=%d is above the supported %d\n", nec, DWPA_NC_MAX);
-        return DWPA_RC_ERROR;
-    }
+    if (!crack_check_args(cfg, nec)) return DWPA_RC_ERROR;
     // hashcat refuses to start when a wordlist cannot be opened; so does this call, before touching a device, and it
     // names the file (DWPA_E_IO in dict_status): a deterministic input error, which help_crack's drop-in does not retry
     bool unreadable = false;
@@ -555,7 +408,7 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
         if (!f) return DWPA_RC_ERROR;
         fclose(f);
         const size_t ai = 1 - cb->base_index();
-        const int r = read_amplifier(dicts[ai], cb);
+        const int r = read_list(dicts[ai], cb);
         if (r == DWPA_E_OVERFLOW) {
             fprintf(stderr, "[dwpa] list %s: too large to be the amplifier (at most %llu bytes of text and offsets, "
                             "fewer than 2^32 words); take the other list with amp_side %d (--amplifier %s)\n",
@@ -569,26 +422,13 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
             fprintf(stderr, "[dwpa] dictionary %s: read error\n", dicts[ai]);
             return DWPA_RC_ERROR;
         }
+        cb->count_lengths();
     }
-    // the config applies to this call only (dwpa_init's process-wide selection stays as it is)
-    if (engine_init() < 0) return DWPA_RC_ERROR;
-    std::vector<int> devs = engine_devices(DWPA_CFG_HAS(cfg, device_mask) ? cfg->device_mask : 0);
-    if (devs.empty()) return DWPA_RC_ERROR;
-    const int nc_mode = DWPA_CFG_HAS(cfg, nc_mode) ? cfg->nc_mode : DWPA_NC_HASHCAT;
-
-    std::vector<std::string> lines;
-    if (!read_hash_file(hash_file, lines)) return DWPA_RC_ERROR;
+    CrackPlan plan;
+    if (!crack_plan(cfg, nec, &plan)) return DWPA_RC_ERROR;
     CrackShared sh;
-    sh.parsed.resize(lines.size());
-    sh.cracked.assign(lines.size(), 0);
-    for (size_t i = 0; i < lines.size(); i++) {
-        sh.parsed[i] = parse_m22000(lines[i].data(), lines[i].size());
-        // rejected by the parser (hashcat: token exception), or a PMKID/MIC shorter than 16 bytes that can never
-        // verify (hashcat refuses such a hash at load time): neither is counted, so rc 0 stays reachable
-        if (sh.parsed[i].status || !line_can_match(sh.parsed[i])) sh.cracked[i] = 1;
-        else sh.valid++;
-    }
-    if (sh.valid == 0) return DWPA_RC_ERROR;  // hashcat: "No hashes loaded"
+    HashLines hl;
+    if (!sh.load_hashes(hash_file, &hl)) return DWPA_RC_ERROR;
 
     // hashcat -r: lines that do not parse -- and, in the default DWPA_RULES_HASHCAT mode, lines using reject or
     // memory functions, which hashcat's -r loader skips too -- are skipped with a message each (RuleSet::add_line)
@@ -600,38 +440,31 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
     const RuleSet* rp = nullptr;
     if (rules_file) {
         const int lr = rules.load_file(rules_file);
-        g_last_stats.rules = (uint32_t)rules.size();
-        g_last_stats.rules_skipped = (uint32_t)rules.skipped.size();
-        g_last_stats.rules_rejmem = rules.rejmem;
+        call.st.rules = (uint32_t)rules.size();
+        call.st.rules_skipped = (uint32_t)rules.skipped.size();
+        call.st.rules_rejmem = rules.rejmem;
+        crack_publish_stats(call.st, {});  // whatever becomes of the call
         if (lr < 0) return DWPA_RC_ERROR;
         if (!rules.all_noop()) rp = &rules;
     }
 
-    sh.out = fopen(out_file, "ab");
-    if (!sh.out) return DWPA_RC_ERROR;
+    if (!sh.open_out(out_file)) return DWPA_RC_ERROR;
 
-    std::vector<const char*> lp(lines.size());
-    std::vector<size_t> ll(lines.size());
-    for (size_t i = 0; i < lines.size(); i++) { lp[i] = lines[i].data(); ll[i] = lines[i].size(); }
-    const uint32_t batch = DWPA_CFG_HAS(cfg, batch) && cfg->batch ? cfg->batch : engine_batch();
-    const size_t spd = crack_shards_per_device();
+    const uint32_t batch = plan.batch;
     std::vector<std::unique_ptr<DevWork>> work;
     int rc = 0;
-    for (int dev : devs)
-        for (size_t k = 0; k < spd && rc >= 0; k++) {
+    for (int dev : plan.devs)
+        for (size_t k = 0; k < plan.shards && rc >= 0; k++) {
             work.push_back(std::make_unique<DevWork>());
             DevWork& w = *work.back();
-            w.device = dev;
-            (void)hipSetDevice(dev);
-            if (hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking) != hipSuccess ||
-                hipStreamCreateWithFlags(&w.up, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&w.staged[0], hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&w.staged[1], hipEventDisableTiming) != hipSuccess)
+            rc = scan_worker_open(w, dev, hl, plan);
+            if (rc >= 0 && (hipStreamCreateWithFlags(&w.up, hipStreamNonBlocking) != hipSuccess ||
+                            hipEventCreateWithFlags(&w.staged[0], hipEventDisableTiming) != hipSuccess ||
+                            hipEventCreateWithFlags(&w.staged[1], hipEventDisableTiming) != hipSuccess))
                 rc = DWPA_E_HIP;
-            if (rc >= 0) rc = scan_create(dev, lp.data(), ll.data(), lines.size(), nec, nc_mode, batch, &w.scan);
             if (rc >= 0 && rp) rc = rules_upload(dev, rules, &w.rules);
             if (rc >= 0 && hy) rc = scan_set_mask(w.scan, *hy->mask);
-            if (rc >= 0 && cb) rc = upload_amplifier(w, *cb);
+            if (rc >= 0 && cb) rc = upload_list(*cb, &w.amp_off, &w.amp_bytes);
         }
     const size_t G = work.size();
     if (rc >= 0 && cb && cb->words() > scan_batch_cap(work[0]->scan)) cb->count_ranges(scan_batch_cap(work[0]->scan));
@@ -670,8 +503,7 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
         }
     };
     auto fail = [&](int r) {
-        int z = 0;
-        sh.error.compare_exchange_strong(z, r);
+        sh.fail(r);
         stop_all();
     };
     std::vector<std::thread> th;
@@ -758,7 +590,7 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
             dict_status[i] = fst[k] == ChunkSource::FILE_DAMAGED ? DWPA_DICT_DAMAGED
                              : fst[k] == ChunkSource::FILE_UNREADABLE ? DWPA_E_IO : DWPA_DICT_OK;
     }
-    if (cb && cb->status == DWPA_DICT_DAMAGED) {
+    if (cb && cb->damaged) {
         const size_t ai = 1 - cb->base_index();
         fprintf(stderr, "[dwpa] dictionary %s: damaged gzip stream (truncated or corrupt); joined up to the damage\n",
                 dicts[ai]);
@@ -771,10 +603,10 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
             fprintf(stderr, "[dwpa] crack worker %zu (device %d): %zu items, %zu words, %.3f s waiting for input of %.3f s\n",
                     k, work[k]->device, work[k]->items, work[k]->words, work[k]->wait_s, el);
     }
+    std::vector<dwpa_crack_worker> wst;
     for (auto& wp : work) {
         DevWork& w = *wp;
-        if (w.scan) scan_destroy(w.scan);
-        (void)hipSetDevice(w.device);
+        scan_worker_close(w);  // waits for the device: the worker's buffers are free after it
         for (int q = 0; q < 2; q++) {
             w.off[q].release();
             w.bytes[q].release();
@@ -783,21 +615,10 @@ static int crack_impl(const char* hash_file, const char* const* dicts, size_t nd
         w.amp_off.release();
         w.amp_bytes.release();
         rules_release(&w.rules);
-        if (w.stream) (void)hipStreamDestroy(w.stream);
         if (w.up) (void)hipStreamDestroy(w.up);
+        wst.push_back(dwpa_crack_worker{w.device, (uint32_t)w.items, (uint64_t)w.words, w.cands, w.wait_s, w.scan_s});
     }
-    fclose(sh.out);
-    for (auto& wp : work) {
-        g_last_stats.words += wp->words;
-        g_last_stats.candidates += wp->cands;
-        g_last_workers.push_back(dwpa_crack_worker{wp->device, (uint32_t)wp->items, (uint64_t)wp->words, wp->cands,
-                                                   wp->wait_s, wp->scan_s});
-    }
-    g_last_stats.hashes = (uint32_t)sh.valid;
-    g_last_stats.cracked = (uint32_t)sh.ncracked;
-    g_last_stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
-    if (rc < 0 || sh.error.load() < 0 || ioerr) return DWPA_RC_ERROR;
-    return sh.ncracked == sh.valid ? DWPA_RC_CRACKED : DWPA_RC_EXHAUSTED;
+    return call.finish(sh, wst, rc < 0 || ioerr);
 }
 
 // `hashcat --stdout -r rules_file sources... -o out_path` (help_crack.py:508 expandcracked, :575 prdict): the words
@@ -994,19 +815,6 @@ void dwpa_debug_crack_loads(uint64_t out[4], int reset) {
                                  : c[i]->load(std::memory_order_relaxed);
         if (out) out[i] = v;
     }
-}
-
-int dwpa_crack_last_stats(dwpa_crack_stats* out) {
-    if (!out || !dwpa::g_have_stats) return DWPA_E_ARG;
-    *out = dwpa::g_last_stats;
-    return 0;
-}
-
-int dwpa_crack_worker_stats(dwpa_crack_worker* out, size_t cap, size_t* n) {
-    if (!n || (!out && cap) || !dwpa::g_have_stats) return DWPA_E_ARG;
-    *n = dwpa::g_last_workers.size();
-    for (size_t i = 0; i < std::min(cap, *n); i++) out[i] = dwpa::g_last_workers[i];
-    return 0;
 }
 
 int dwpa_crack_files_ex(const char* hash_file, const char* const* dicts, size_t ndicts, const char* rules_file,

@@ -1,0 +1,364 @@
+// crack_range.cpp -- the two attacks over a range of indices, with dwpa_crack_files' hash file, rc convention, outfile
+// records, nc-mode default and cfg handling (crack_common.hpp):
+//   dwpa_crack_mask():  hashcat -a 3.  The keyspace is a list of segments, one per mask length that runs: the mask
+//                       itself, or with increment its prefixes, shortest first.
+//   dwpa_crack_chain(): a chain of 1..4 word lists and masks (chain.hpp).  Every list is read whole through the
+//                       dictionary reader once (plain or gzip, CRLF, $HEX[]), kept on the host to rebuild a hit's PSK
+//                       and uploaded once per worker.  The keyspace is one segment of raw indices [skip, skip + limit).
+//
+// There is no dictionary feed, so none of crack.cpp's reader / item-queue machinery: every worker --
+// DWPA_CRACK_SHARDS_PER_DEVICE per selected device -- takes batch-sized ascending index ranges from one shared cursor
+// (crack_cursor.hpp), generates them on its device, scans them and reports.  A hit's PSK is rebuilt on the host from
+// its index; the first hit of a line is written once, under the mutex, and the line is retired on every worker before
+// its next launch.  A fully cracked file stops every worker.
+//
+// One driver runs both.  An attack is a type with the segments' meaning in it and a nested Worker, one per scan worker:
+//   Worker(attack)            its state (the mask attack: the prefix its scan holds)
+//   open(w)                   once, before any thread runs (the chain attack: upload the lists, scan_set_chain)
+//   enter(w, seg)             before the first load of a segment
+//   load(w, first, count)     generate indices [first, first + count) of the segment into w's scan
+//   counted(w, count, &n)     the candidates of the load just scanned; the stream is idle
+//   plain_of(id, &psk)        the PSK of candidate id of the segment; false for an id outside it
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "dwpa22000.h"
+#include "chain.hpp"
+#include "crack_common.hpp"
+#include "crack_cursor.hpp"
+#include "engine.hpp"
+#include "mask.hpp"
+
+namespace dwpa {
+
+namespace {
+
+template <class AttackWorker>
+int range_worker(ScanWorker& w, AttackWorker& aw, CrackShared& sh, RangeCursor& cursor) {
+    if (hipSetDevice(w.device) != hipSuccess) return DWPA_E_HIP;
+    const uint32_t cap = scan_batch_cap(w.scan);
+    size_t cur_seg = (size_t)-1, seg;
+    uint64_t first;
+    uint32_t count;
+    std::vector<HitDev> hits;
+    while (!sh.stop.load(std::memory_order_relaxed) && cursor.take(cap, &seg, &first, &count)) {
+        const auto ts = std::chrono::steady_clock::now();
+        int r;
+        if (seg != cur_seg) {
+            if ((r = aw.enter(w, seg)) < 0) return r;
+            cur_seg = seg;
+        }
+        if ((r = aw.load(w, first, count)) < 0) return r;
+        if ((r = scan_step(w, sh, hits, [&](uint64_t id, std::string* psk) { return aw.plain_of(id, psk); })) < 0)
+            return r;
+        uint64_t n = 0;
+        if ((r = aw.counted(w, count, &n)) < 0) return r;
+        w.items++;
+        w.cands += n;
+        w.scan_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
+    }
+    return 0;
+}
+
+// From the first device touched to the return code.  Everything an attack can refuse on the host has been refused.
+template <class Attack>
+int crack_range(CrackCall& call, const char* hash_file, int nec, const char* out_file, const dwpa_config* cfg,
+                std::vector<RangeSegment> segs, const Attack& attack) {
+    CrackPlan plan;
+    if (!crack_plan(cfg, nec, &plan)) return DWPA_RC_ERROR;
+    CrackShared sh;
+    HashLines hl;
+    if (!sh.load_hashes(hash_file, &hl) || !sh.open_out(out_file)) return DWPA_RC_ERROR;
+
+    struct Work {
+        ScanWorker scan;
+        typename Attack::Worker attack;
+        explicit Work(const Attack& a) : attack(a) {}
+    };
+    std::vector<std::unique_ptr<Work>> work;
+    int rc = 0;
+    for (int dev : plan.devs)
+        for (size_t k = 0; k < plan.shards && rc >= 0; k++) {
+            work.push_back(std::make_unique<Work>(attack));
+            Work& w = *work.back();
+            if ((rc = scan_worker_open(w.scan, dev, hl, plan)) >= 0) rc = w.attack.open(w.scan);
+        }
+    RangeCursor cursor(std::move(segs));
+    if (rc >= 0)
+        run_workers(sh, work.size(), [&](size_t k) { return range_worker(work[k]->scan, work[k]->attack, sh, cursor); });
+    std::vector<dwpa_crack_worker> wst;
+    for (auto& wp : work) {
+        ScanWorker& w = wp->scan;
+        scan_worker_close(w);  // waits for the device: what the attack's worker holds there is free after it
+        wst.push_back(dwpa_crack_worker{w.device, (uint32_t)w.items, 0, w.cands, 0.0, w.scan_s});
+    }
+    return call.finish(sh, wst, rc < 0);
+}
+
+struct MaskAttack {
+    const Mask& full;
+    std::vector<uint32_t> npos;  // per segment: the positions of its prefix
+
+    struct Worker {
+        const MaskAttack& at;
+        std::unique_ptr<Mask> cur = std::make_unique<Mask>();  // the prefix this worker's scan holds
+        explicit Worker(const MaskAttack& a) : at(a) {}
+        int open(ScanWorker&) { return 0; }
+        int enter(ScanWorker& w, size_t seg) {
+            mask_prefix(at.full, at.npos[seg], cur.get());
+            return scan_set_mask(w.scan, *cur);
+        }
+        int load(ScanWorker& w, uint64_t first, uint32_t count) { return scan_load_mask(w.scan, first, count, w.stream); }
+        int counted(ScanWorker&, uint32_t count, uint64_t* n) {
+            *n = count;  // every index is a candidate: nothing to read back
+            return 0;
+        }
+        bool plain_of(uint64_t id, std::string* psk) const {
+            if (id >= cur->keyspace) return false;
+            uint8_t m[64];
+            mask_candidate(*cur, id, m);
+            psk->assign((const char*)m, cur->npos);
+            return true;
+        }
+    };
+};
+
+int crack_mask_impl(const char* hash_file, const char* mask, const dwpa_bytes* custom, uint64_t skip, uint64_t limit,
+                    uint32_t inc_min, uint32_t inc_max, int nec, const char* out_file, const dwpa_config* cfg) {
+    CrackCall call;
+    if (!hash_file || !mask || !out_file) return DWPA_RC_ERROR;
+    if (!crack_check_args(cfg, nec)) return DWPA_RC_ERROR;
+    auto full = std::make_unique<Mask>();
+    if (mask_parse(mask, strlen(mask), custom, full.get()) < 0) {
+        fprintf(stderr, "[dwpa] mask %s: invalid (syntax, an undefined custom set, more than 63 positions or a keyspace "
+                        "above 2^64 - 1)\n", mask);
+        return DWPA_RC_ERROR;
+    }
+    const bool increment = inc_min || inc_max;
+    if (increment && (skip || limit)) {
+        fprintf(stderr, "[dwpa] --increment cannot be combined with --skip / --limit\n");
+        return DWPA_RC_ERROR;
+    }
+    MaskAttack attack{*full, {}};
+    std::vector<RangeSegment> segs;
+    if (increment) {
+        const uint32_t lo = std::max<uint32_t>(1, inc_min), hi = std::min(inc_max ? inc_max : full->npos, full->npos);
+        if (lo > hi) return DWPA_RC_ERROR;
+        auto pre = std::make_unique<Mask>();
+        for (uint32_t n = lo; n <= hi; n++) {
+            if (n < 8) {  // hashcat skips a mask shorter than the hash mode's shortest password
+                fprintf(stderr, "[dwpa] skipping the mask's first %u positions: m22000 takes 8..63 characters\n", n);
+                continue;
+            }
+            mask_prefix(*full, n, pre.get());
+            attack.npos.push_back(n);
+            segs.push_back(RangeSegment{0, pre->keyspace});
+        }
+    } else if (full->npos < 8) {
+        fprintf(stderr, "[dwpa] skipping mask %s: %u positions, m22000 takes 8..63 characters\n", mask, full->npos);
+    } else {
+        if (skip >= full->keyspace) {
+            fprintf(stderr, "[dwpa] --skip is not below the keyspace\n");
+            return DWPA_RC_ERROR;
+        }
+        const uint64_t room = full->keyspace - skip;
+        attack.npos.push_back(full->npos);
+        segs.push_back(RangeSegment{skip, skip + (limit && limit < room ? limit : room)});
+    }
+    if (segs.empty()) return DWPA_RC_ERROR;  // nothing left to run
+    return crack_range(call, hash_file, nec, out_file, cfg, std::move(segs), attack);
+}
+
+struct ChainPart {
+    std::unique_ptr<Mask> mask;  // a mask part, else a list
+    HostList list;
+    uint64_t radix = 0;
+};
+
+struct ChainAttack {
+    const dwpa_chain_spec* specs;
+    const dwpa_bytes* custom;
+    std::vector<ChainPart> parts;
+    uint64_t radix[CHAIN_MAX_PARTS] = {};
+    uint64_t K = 0;
+
+    // Candidate `id` (< K) as its bytes: the parts' choices left to right.
+    bool candidate(uint64_t id, std::string* psk) const {
+        uint64_t digit[CHAIN_MAX_PARTS];
+        if (chain_split(radix, (uint32_t)parts.size(), id, digit) < 0) return false;
+        psk->clear();
+        for (size_t p = 0; p < parts.size(); p++) {
+            const ChainPart& cp = parts[p];
+            if (cp.mask) {
+                uint8_t m[64];
+                mask_candidate(*cp.mask, digit[p], m);
+                psk->append((const char*)m, cp.mask->npos);
+            } else {
+                const HostList& l = cp.list;
+                psk->append(l.bytes, (size_t)l.off[digit[p]], (size_t)(l.off[digit[p] + 1] - l.off[digit[p]]));
+            }
+        }
+        return true;
+    }
+
+    struct Worker {
+        const ChainAttack& at;
+        int device = 0;
+        DevBuf off[CHAIN_MAX_PARTS], bytes[CHAIN_MAX_PARTS];  // the lists on this worker's device
+        explicit Worker(const ChainAttack& a) : at(a) {}
+        ~Worker() {
+            (void)hipSetDevice(device);
+            for (uint32_t p = 0; p < CHAIN_MAX_PARTS; p++) {
+                off[p].release();
+                bytes[p].release();
+            }
+        }
+        int open(ScanWorker& w) {
+            device = w.device;
+            dwpa_chain_part cp[CHAIN_MAX_PARTS] = {};
+            for (size_t p = 0; p < at.parts.size(); p++) {
+                if (at.parts[p].mask) {
+                    cp[p].kind = DWPA_CHAIN_MASK;
+                    cp[p].mask = at.specs[p].text;
+                    cp[p].mask_len = strlen(at.specs[p].text);
+                    continue;
+                }
+                const int r = upload_list(at.parts[p].list, &off[p], &bytes[p]);
+                if (r < 0) return r;
+                cp[p].kind = DWPA_CHAIN_LIST;
+                cp[p].d_offsets = (const uint64_t*)off[p].p;
+                cp[p].d_bytes = (const uint8_t*)bytes[p].p;
+                cp[p].nwords = at.parts[p].radix;
+            }
+            return scan_set_chain(w.scan, cp, (uint32_t)at.parts.size(), at.custom, nullptr);
+        }
+        int enter(ScanWorker&, size_t) { return 0; }
+        // A load is `count` raw indices, so PBKDF2 runs over the kept ones only: a chain whose filter drops most
+        // candidates runs short launches (filling a batch from several raw ranges is left for later).
+        int load(ScanWorker& w, uint64_t first, uint32_t count) {
+            return scan_load_chain(w.scan, first, count, 8, 63, w.stream);
+        }
+        int counted(ScanWorker& w, uint32_t, uint64_t* n) {
+            uint32_t kept = 0;  // the stream is idle by now: this copy waits for nothing
+            const int r = scan_counter_raw(w.scan, w.stream, &kept);
+            *n = kept;
+            return r;
+        }
+        bool plain_of(uint64_t id, std::string* psk) const { return id < at.K && at.candidate(id, psk); }
+    };
+};
+
+int crack_chain_impl(const char* hash_file, const dwpa_chain_spec* specs, uint32_t nparts, const dwpa_bytes* custom,
+                     uint64_t skip, uint64_t limit, int nec, const char* out_file, const dwpa_config* cfg,
+                     int32_t* part_status) {
+    CrackCall call;
+    if (nparts == 0 || nparts > CHAIN_MAX_PARTS) {
+        fprintf(stderr, "[dwpa] a chain takes 1..%u parts\n", CHAIN_MAX_PARTS);
+        return DWPA_RC_ERROR;
+    }
+    if (part_status)
+        for (uint32_t p = 0; p < nparts; p++) part_status[p] = DWPA_DICT_OK;
+    if (!hash_file || !specs || !out_file) return DWPA_RC_ERROR;
+    if (!crack_check_args(cfg, nec)) return DWPA_RC_ERROR;
+    // every part is looked at before the call fails, so that each unreadable list is marked
+    ChainAttack attack{specs, custom, {}};
+    std::vector<ChainPart>& parts = attack.parts;
+    parts.resize(nparts);
+    bool bad = false;
+    for (uint32_t p = 0; p < nparts; p++) {
+        const char* text = specs[p].text;
+        if (specs[p].kind == DWPA_CHAIN_MASK) {
+            parts[p].mask = std::make_unique<Mask>();
+            if (!text || mask_parse(text, strlen(text), custom, parts[p].mask.get()) < 0) {
+                fprintf(stderr, "[dwpa] part %u, mask %s: invalid (syntax, an undefined custom set, more than 63 "
+                                "positions or a keyspace above 2^64 - 1)\n", p + 1, text ? text : "(null)");
+                bad = true;
+            } else {
+                parts[p].radix = parts[p].mask->keyspace;
+            }
+        } else if (specs[p].kind == DWPA_CHAIN_LIST) {
+            FILE* f = text ? fopen(text, "rb") : nullptr;
+            if (!f) {
+                if (part_status) part_status[p] = DWPA_E_IO;
+                fprintf(stderr, "[dwpa] part %u, list %s: cannot be opened\n", p + 1, text ? text : "(null)");
+                bad = true;
+            } else {
+                fclose(f);
+            }
+        } else {
+            fprintf(stderr, "[dwpa] part %u: kind %d is neither a list nor a mask\n", p + 1, specs[p].kind);
+            bad = true;
+        }
+    }
+    if (bad) return DWPA_RC_ERROR;
+    {
+        FILE* f = fopen(hash_file, "rb");
+        if (!f) return DWPA_RC_ERROR;
+        fclose(f);
+    }
+    for (uint32_t p = 0; p < nparts; p++) {
+        if (!parts[p].mask) {
+            const int r = read_list(specs[p].text, &parts[p].list);
+            if (r == DWPA_E_OVERFLOW) {
+                fprintf(stderr, "[dwpa] part %u, list %s: too large to hold (at most %llu bytes of text and offsets, "
+                                "fewer than 2^32 words)\n", p + 1, specs[p].text,
+                        (unsigned long long)DWPA_COMBI_AMP_MAX_BYTES);
+                return DWPA_RC_ERROR;
+            }
+            if (r < 0) {
+                if (part_status) part_status[p] = DWPA_E_IO;
+                fprintf(stderr, "[dwpa] part %u, list %s: read error\n", p + 1, specs[p].text);
+                return DWPA_RC_ERROR;
+            }
+            if (parts[p].list.damaged && part_status) part_status[p] = DWPA_DICT_DAMAGED;
+            parts[p].radix = parts[p].list.words();
+            call.st.words += parts[p].radix;
+        }
+        attack.radix[p] = parts[p].radix;
+    }
+    if (chain_keyspace(attack.radix, nparts, &attack.K) < 0) {
+        fprintf(stderr, "[dwpa] the chain's keyspace is above 2^64 - 1\n");
+        return DWPA_RC_ERROR;
+    }
+    const uint64_t K = attack.K;
+    if (K > 0 && skip >= K) {
+        fprintf(stderr, "[dwpa] --skip is not below the keyspace\n");
+        return DWPA_RC_ERROR;
+    }
+    std::vector<RangeSegment> segs;  // K = 0 (an empty list): nothing to run, the call exhausts
+    if (K > 0) {
+        const uint64_t room = K - skip;
+        segs.push_back(RangeSegment{skip, skip + (limit && limit < room ? limit : room)});
+    }
+    return crack_range(call, hash_file, nec, out_file, cfg, std::move(segs), attack);
+}
+
+}  // namespace
+
+}  // namespace dwpa
+
+extern "C" int dwpa_crack_mask(const char* hash_file, const char* mask, const dwpa_bytes custom[4], uint64_t skip,
+                               uint64_t limit, uint32_t increment_min, uint32_t increment_max,
+                               int nonce_error_corrections, const char* out_file, const dwpa_config* cfg) {
+    return dwpa::guarded([&]() -> int {
+        return dwpa::crack_mask_impl(hash_file, mask, custom, skip, limit, increment_min, increment_max,
+                                     nonce_error_corrections, out_file, cfg);
+    }, DWPA_RC_ERROR, DWPA_RC_ERROR);
+}
+
+extern "C" int dwpa_crack_chain(const char* hash_file, const dwpa_chain_spec* parts, uint32_t nparts,
+                                const dwpa_bytes custom[4], uint64_t skip, uint64_t limit,
+                                int nonce_error_corrections, const char* out_file, const dwpa_config* cfg,
+                                int32_t* part_status) {
+    return dwpa::guarded([&]() -> int {
+        return dwpa::crack_chain_impl(hash_file, parts, nparts, custom, skip, limit, nonce_error_corrections,
+                                      out_file, cfg, part_status);
+    }, DWPA_RC_ERROR, DWPA_RC_ERROR);
+}

@@ -1,5 +1,5 @@
-// engine.hpp -- internal interfaces of libdwpa22000.so shared by engine.cpp, crack.cpp, crack_mask.cpp and
-// crack_chain.cpp.
+// engine.hpp -- the engine's own interface inside libdwpa22000.so (engine.cpp), as the host backend, the rule engine
+// and the crack calls (crack_common.hpp, crack.cpp, crack_range.cpp) use it.
 #pragma once
 #include <stdint.h>
 
@@ -123,14 +123,5 @@ uint32_t scan_batch_cap(const dwpa_scan* sc);
 Batch& scan_batch_ref(dwpa_scan* sc);
 int scan_device(const dwpa_scan* sc);
 void scan_rules_drop(const dwpa_scan* scan);
-
-
-// crack.cpp helpers shared with crack_mask.cpp
-struct ParsedLine;  // m22000_host.hpp
-std::string outfile_record(const ParsedLine& p, const std::string& psk);
-size_t crack_shards_per_device();  // DWPA_CRACK_SHARDS_PER_DEVICE, 1..8
-bool read_hash_file(const char* path, std::vector<std::string>& lines);
-// what dwpa_crack_last_stats / dwpa_crack_worker_stats report for the calling thread from now on
-void crack_publish_stats(const dwpa_crack_stats& st, const std::vector<dwpa_crack_worker>& workers);
 
 }  // namespace dwpa

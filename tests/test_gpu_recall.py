@@ -436,7 +436,7 @@ def _plain(b):
 
 
 def _records(lines, psks):
-    """The outfile record of each line: MIC or PMKID : AP : STA : ESSID : PSK (crack.cpp outfile_record)."""
+    """The outfile record of each line: MIC or PMKID : AP : STA : ESSID : PSK (crack_common.cpp outfile_record)."""
     out = []
     for line, psk in zip(lines, psks):
         f = line.split(b"*")
