@@ -9,7 +9,8 @@ HDRS := $(wildcard $(SRC)/*.hpp) include/dwpa22000.h
 OBJS := $(OBJ)/kernels.o $(OBJ)/rules_dev.o $(OBJ)/engine.o $(OBJ)/m22000_host.o $(OBJ)/crack.o $(OBJ)/rules.o \
         $(OBJ)/pbkdf2_module.o $(OBJ)/pbkdf2_hsaco.o $(OBJ)/host_crypto.o $(OBJ)/host_check.o \
         $(OBJ)/mask.o $(OBJ)/mask_dev.o $(OBJ)/crack_common.o $(OBJ)/hybrid_dev.o \
-        $(OBJ)/combi_dev.o $(OBJ)/chain.o $(OBJ)/chain_dev.o $(OBJ)/crack_range.o
+        $(OBJ)/combi_dev.o $(OBJ)/chain.o $(OBJ)/chain_dev.o $(OBJ)/chain_rules_dev.o \
+        $(OBJ)/crack_range.o
 LLVM := /opt/rocm/lib/llvm/bin
 ISSUE_RULE ?= sched=1:alt:orig:asmnop,before_half
 # 1: the two work-queue PBKDF2 kernels keep their cold words in LDS (pbkdf2_dev.hpp pbkdf2_lane_lds); 0: the plain lane
@@ -68,13 +69,16 @@ $(LIB): $(OBJS)
 oracle:
 	$(MAKE) -s -C oracle
 
-asm: $(SRC)/kernels.hip $(SRC)/mask_dev.hip $(SRC)/hybrid_dev.hip $(SRC)/combi_dev.hip $(SRC)/chain_dev.hip $(HDRS)
+asm: $(SRC)/kernels.hip $(SRC)/mask_dev.hip $(SRC)/hybrid_dev.hip $(SRC)/combi_dev.hip $(SRC)/chain_dev.hip \
+     $(SRC)/chain_rules_dev.hip $(SRC)/rules_dev.hip $(HDRS)
 	@mkdir -p build/asm
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $< -o build/asm/kernels.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/mask_dev.hip -o build/asm/mask_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/hybrid_dev.hip -o build/asm/hybrid_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/combi_dev.hip -o build/asm/combi_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/chain_dev.hip -o build/asm/chain_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/chain_rules_dev.hip -o build/asm/chain_rules_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/rules_dev.hip -o build/asm/rules_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 
 clean:
 	rm -rf build $(LIB)

@@ -15,7 +15,8 @@ this package is its Python host side:
   (``python -m dwpa_amd.mask -a 1``); :meth:`Scan.load_combinator` is its scan-path load
 * :func:`crack_chain`      -- chain attack, up to four word lists and masks joined left to right
   (``python -m dwpa_amd.chain``); :meth:`Scan.set_chain` / :meth:`Scan.load_chain` are its scan-path calls,
-  :func:`chain_keyspace` / :func:`chain_split` / :func:`chain_candidate` its host-only helpers
+  :func:`chain_keyspace` / :func:`chain_split` / :func:`chain_candidate` its host-only helpers; a list part may
+  carry hashcat rules (``crack_chain(..., rules=)``, :meth:`Scan.set_chain_rules`, ``chain_candidate(..., rules=)``)
 * :mod:`dwpa_amd.help_crack` -- ``run_cracker`` replacement for help_crack.py
 """
 from ._lib import (DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS, DWPA_COMBI_AMP_LEFT,  # noqa: F401

@@ -175,6 +175,12 @@ SIGNATURES = {
     "dwpa_crack_chain": ([ctypes.c_char_p, ctypes.POINTER(ChainSpec), ctypes.c_uint32, ctypes.POINTER(Bytes),
                           ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config),
                           ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
+    "dwpa_scan_set_chain_rules": ([_P, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t,
+                                   ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_crack_chain_rules": ([ctypes.c_char_p, ctypes.POINTER(ChainSpec), ctypes.c_uint32,
+                                ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(Bytes), ctypes.c_uint64,
+                                ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config),
+                                ctypes.POINTER(ctypes.c_int32)], ctypes.c_int),
     "dwpa_crack_mask": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Bytes), ctypes.c_uint64, ctypes.c_uint64,
                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)],
                         ctypes.c_int),

@@ -5,6 +5,9 @@
 //   dwpa_crack_chain(): a chain of 1..4 word lists and masks (chain.hpp).  Every list is read whole through the
 //                       dictionary reader once (plain or gzip, CRLF, $HEX[]), kept on the host to rebuild a hit's PSK
 //                       and uploaded once per worker.  The keyspace is one segment of raw indices [skip, skip + limit).
+//   dwpa_crack_chain_rules(): the same with a rules file on any list part (chain_rules_dev.hip): that part's choices
+//                       are its (rule, word) pairs, rule-major, and a hit's PSK takes the rule through
+//                       RuleSet::apply_host.
 //
 // There is no dictionary feed, so none of crack.cpp's reader / item-queue machinery: every worker --
 // DWPA_CRACK_SHARDS_PER_DEVICE per selected device -- takes batch-sized ascending index ranges from one shared cursor
@@ -35,6 +38,7 @@
 #include "crack_cursor.hpp"
 #include "engine.hpp"
 #include "mask.hpp"
+#include "rules.hpp"
 
 namespace dwpa {
 
@@ -179,6 +183,7 @@ int crack_mask_impl(const char* hash_file, const char* mask, const dwpa_bytes* c
 struct ChainPart {
     std::unique_ptr<Mask> mask;  // a mask part, else a list
     HostList list;
+    std::unique_ptr<RuleSet> rules;  // a ruled list: radix = its word count x its rules
     uint64_t radix = 0;
 };
 
@@ -202,6 +207,15 @@ struct ChainAttack {
                 psk->append((const char*)m, cp.mask->npos);
             } else {
                 const HostList& l = cp.list;
+                if (cp.rules) {  // choice = rule * words + word
+                    const uint64_t nw = l.words(), rule = digit[p] / nw, wi = digit[p] % nw;
+                    std::string piece;
+                    if (!cp.rules->apply_host((size_t)rule, l.bytes.substr((size_t)l.off[wi],
+                                                                           (size_t)(l.off[wi + 1] - l.off[wi])), &piece))
+                        return false;  // cannot happen for a hit: the GPU kept it
+                    psk->append(piece);
+                    continue;
+                }
                 psk->append(l.bytes, (size_t)l.off[digit[p]], (size_t)(l.off[digit[p] + 1] - l.off[digit[p]]));
             }
         }
@@ -235,9 +249,12 @@ struct ChainAttack {
                 cp[p].kind = DWPA_CHAIN_LIST;
                 cp[p].d_offsets = (const uint64_t*)off[p].p;
                 cp[p].d_bytes = (const uint8_t*)bytes[p].p;
-                cp[p].nwords = at.parts[p].radix;
+                cp[p].nwords = at.parts[p].list.words();
             }
-            return scan_set_chain(w.scan, cp, (uint32_t)at.parts.size(), at.custom, nullptr);
+            int r = scan_set_chain(w.scan, cp, (uint32_t)at.parts.size(), at.custom, nullptr);
+            for (size_t p = 0; p < at.parts.size() && r >= 0; p++)
+                if (at.parts[p].rules) r = scan_set_chain_rules(w.scan, (uint32_t)p, at.parts[p].rules.get(), nullptr);
+            return r < 0 ? r : 0;
         }
         int enter(ScanWorker&, size_t) { return 0; }
         // A load is `count` raw indices, so PBKDF2 runs over the kept ones only: a chain whose filter drops most
@@ -255,9 +272,10 @@ struct ChainAttack {
     };
 };
 
-int crack_chain_impl(const char* hash_file, const dwpa_chain_spec* specs, uint32_t nparts, const dwpa_bytes* custom,
-                     uint64_t skip, uint64_t limit, int nec, const char* out_file, const dwpa_config* cfg,
-                     int32_t* part_status) {
+int crack_chain_impl(const char* hash_file, const dwpa_chain_spec* specs, uint32_t nparts,
+                     const char* const* part_rules /* nullable; nparts paths of rules files, nullptr: no rules */,
+                     const dwpa_bytes* custom, uint64_t skip, uint64_t limit, int nec, const char* out_file,
+                     const dwpa_config* cfg, int32_t* part_status) {
     CrackCall call;
     if (nparts == 0 || nparts > CHAIN_MAX_PARTS) {
         fprintf(stderr, "[dwpa] a chain takes 1..%u parts\n", CHAIN_MAX_PARTS);
@@ -276,6 +294,10 @@ int crack_chain_impl(const char* hash_file, const dwpa_chain_spec* specs, uint32
         const char* text = specs[p].text;
         if (specs[p].kind == DWPA_CHAIN_MASK) {
             parts[p].mask = std::make_unique<Mask>();
+            if (part_rules && part_rules[p]) {
+                fprintf(stderr, "[dwpa] part %u: rules go with a list part, not with a mask\n", p + 1);
+                bad = true;
+            }
             if (!text || mask_parse(text, strlen(text), custom, parts[p].mask.get()) < 0) {
                 fprintf(stderr, "[dwpa] part %u, mask %s: invalid (syntax, an undefined custom set, more than 63 "
                                 "positions or a keyspace above 2^64 - 1)\n", p + 1, text ? text : "(null)");
@@ -297,6 +319,23 @@ int crack_chain_impl(const char* hash_file, const dwpa_chain_spec* specs, uint32
             bad = true;
         }
     }
+    if (bad) return DWPA_RC_ERROR;
+    // rules files load under the process's rule mode, as dwpa_crack_files' -r (hashcat's loader unless DWPA_RULES_FULL);
+    // the counts are sums over the parts and are published whatever becomes of the call
+    const int want = DWPA_CFG_HAS(cfg, rule_mode) ? cfg->rule_mode : DWPA_RULES_DEFAULT;
+    if (want != DWPA_RULES_DEFAULT && want != DWPA_RULES_HASHCAT && want != DWPA_RULES_FULL) return DWPA_RC_ERROR;
+    for (uint32_t p = 0; p < nparts; p++) {
+        if (!part_rules || !part_rules[p]) continue;
+        parts[p].rules = std::make_unique<RuleSet>();
+        parts[p].rules->mode = want == DWPA_RULES_DEFAULT ? engine_rule_mode() : want;
+        const int lr = parts[p].rules->load_file(part_rules[p]);
+        if (lr == DWPA_E_IO) fprintf(stderr, "[dwpa] part %u, rules %s: cannot be opened\n", p + 1, part_rules[p]);
+        call.st.rules += (uint32_t)parts[p].rules->size();
+        call.st.rules_skipped += (uint32_t)parts[p].rules->skipped.size();
+        call.st.rules_rejmem += parts[p].rules->rejmem;
+        bad |= lr < 0;
+    }
+    if (part_rules) crack_publish_stats(call.st, {});
     if (bad) return DWPA_RC_ERROR;
     {
         FILE* f = fopen(hash_file, "rb");
@@ -320,6 +359,14 @@ int crack_chain_impl(const char* hash_file, const dwpa_chain_spec* specs, uint32
             if (parts[p].list.damaged && part_status) part_status[p] = DWPA_DICT_DAMAGED;
             parts[p].radix = parts[p].list.words();
             call.st.words += parts[p].radix;
+            if (parts[p].rules) {
+                parts[p].radix *= parts[p].rules->size();  // < 2^32 words x a rule count that fits memory: no wrap
+                if (parts[p].radix > UINT32_MAX) {
+                    fprintf(stderr, "[dwpa] part %u: %llu words x %zu rules is 2^32 choices or more\n", p + 1,
+                            (unsigned long long)parts[p].list.words(), parts[p].rules->size());
+                    return DWPA_RC_ERROR;
+                }
+            }
         }
         attack.radix[p] = parts[p].radix;
     }
@@ -358,7 +405,17 @@ extern "C" int dwpa_crack_chain(const char* hash_file, const dwpa_chain_spec* pa
                                 int nonce_error_corrections, const char* out_file, const dwpa_config* cfg,
                                 int32_t* part_status) {
     return dwpa::guarded([&]() -> int {
-        return dwpa::crack_chain_impl(hash_file, parts, nparts, custom, skip, limit, nonce_error_corrections,
-                                      out_file, cfg, part_status);
+        return dwpa::crack_chain_impl(hash_file, parts, nparts, nullptr, custom, skip, limit,
+                                      nonce_error_corrections, out_file, cfg, part_status);
+    }, DWPA_RC_ERROR, DWPA_RC_ERROR);
+}
+
+extern "C" int dwpa_crack_chain_rules(const char* hash_file, const dwpa_chain_spec* parts, uint32_t nparts,
+                                      const char* const* part_rules, const dwpa_bytes custom[4], uint64_t skip,
+                                      uint64_t limit, int nonce_error_corrections, const char* out_file,
+                                      const dwpa_config* cfg, int32_t* part_status) {
+    return dwpa::guarded([&]() -> int {
+        return dwpa::crack_chain_impl(hash_file, parts, nparts, part_rules, custom, skip, limit,
+                                      nonce_error_corrections, out_file, cfg, part_status);
     }, DWPA_RC_ERROR, DWPA_RC_ERROR);
 }

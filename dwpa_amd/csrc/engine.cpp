@@ -35,6 +35,7 @@
 #include "m22000_host.hpp"
 #include "mask.hpp"
 #include "chain.hpp"
+#include "rules.hpp"
 
 namespace dwpa {
 
@@ -1486,12 +1487,14 @@ struct dwpa_scan {
     dwpa::DevBuf mask_tab;
     // dwpa_scan_set_chain: the parts as given (the lists' device pointers are the caller's), the parsed mask of every
     // mask part (host copy: dwpa_scan_load_chain decomposes `first` with it) and one device table each; mask_tab is not
-    // touched
+    // touched.  dwpa_scan_set_chain_rules: a list part's rule set on the device; its radix is then nwords * nrules.
     struct ChainPart {
         bool is_mask = false;
         const uint64_t* off = nullptr;
         const uint8_t* bytes = nullptr;
         uint64_t radix = 0;
+        uint64_t nwords = 0;   // a list's word count
+        dwpa::DevRules rules;  // nrules 0: no rules
         std::unique_ptr<dwpa::Mask> mask;
         dwpa::DevBuf tab;
     };
@@ -1568,7 +1571,10 @@ void scan_destroy(dwpa_scan* sc) {
     sc->lines.release(); sc->atts.release(); sc->pool.release(); sc->salt.release(); sc->segs.release();
     sc->mg_pmk.release(); sc->mg_gsalt.release(); sc->mg_list.release(); sc->mg_poff.release();
     sc->mask_tab.release();
-    for (auto& cp : sc->chain) cp.tab.release();
+    for (auto& cp : sc->chain) {
+        cp.tab.release();
+        rules_release(&cp.rules);
+    }
     sc->batch.mid.release(); sc->batch.pmk.release(); sc->batch.ids.release(); sc->batch.hits.release();
     sc->batch.counters.release();
     delete sc;
@@ -1687,7 +1693,8 @@ int scan_load_combinator(dwpa_scan* sc, const uint64_t* base_off, const uint8_t*
 }
 
 // A chain of 1..4 parts (chain_dev.hip).  Everything is parsed and checked before the scan changes, so a refused call
-// leaves the previous chain set; a new chain replaces it after the launches that still read the old tables are done.
+// leaves the previous chain set; a new chain replaces it after the launches that still read the old tables are done,
+// and carries no rules.
 int scan_set_chain(dwpa_scan* sc, const dwpa_chain_part* parts, uint32_t nparts, const dwpa_bytes* custom,
                    uint64_t* keyspace) {
     if (!sc || !parts || nparts == 0 || nparts > CHAIN_MAX_PARTS) return DWPA_E_ARG;
@@ -1710,6 +1717,10 @@ int scan_set_chain(dwpa_scan* sc, const dwpa_chain_part* parts, uint32_t nparts,
     HIPCHK(hipSetDevice(sc->device));
     HIPCHK(hipDeviceSynchronize());
     sc->chain_set = false;
+    for (auto& cp : sc->chain) {  // a new chain carries no rules
+        rules_release(&cp.rules);
+        cp.rules = DevRules();
+    }
     std::vector<uint8_t> tab(MASK_TABLE_BYTES);
     for (uint32_t p = 0; p < nparts; p++) {
         dwpa_scan::ChainPart& cp = sc->chain[p];
@@ -1717,6 +1728,7 @@ int scan_set_chain(dwpa_scan* sc, const dwpa_chain_part* parts, uint32_t nparts,
         cp.off = parts[p].d_offsets;
         cp.bytes = parts[p].d_bytes;
         cp.radix = radix[p];
+        cp.nwords = cp.is_mask ? 0 : radix[p];
         if (cp.is_mask) {
             mask_table(*masks[p], tab.data());
             RCHK(cp.tab.ensure(MASK_TABLE_BYTES));
@@ -1731,8 +1743,39 @@ int scan_set_chain(dwpa_scan* sc, const dwpa_chain_part* parts, uint32_t nparts,
     return 0;
 }
 
+// Rules on list part `part` of the scan's chain (chain_rules_dev.hip); rs == nullptr or an empty set takes them off.
+// Every check is host arithmetic on what the scan holds: neither list nor device is read before the call can still be
+// refused, and a refused call leaves the chain and every part's rules as they were.
+int scan_set_chain_rules(dwpa_scan* sc, uint32_t part, const RuleSet* rs, uint64_t* keyspace) {
+    if (!sc || !sc->chain_set || part >= sc->chain_nparts || sc->chain[part].is_mask) return DWPA_E_ARG;
+    dwpa_scan::ChainPart& cp = sc->chain[part];
+    const uint64_t nrules = rs ? rs->size() : 0;
+    uint64_t choices = cp.nwords;
+    if (nrules && (__builtin_mul_overflow(cp.nwords, nrules, &choices) || choices > UINT32_MAX)) return DWPA_E_ARG;
+    uint64_t radix[CHAIN_MAX_PARTS], K;
+    for (uint32_t p = 0; p < sc->chain_nparts; p++) radix[p] = p == part ? choices : sc->chain[p].radix;
+    RCHK(chain_keyspace(radix, sc->chain_nparts, &K));
+    DevRules dev;
+    if (nrules) {
+        const int r = rules_upload(sc->device, *rs, &dev);
+        if (r < 0) {
+            rules_release(&dev);
+            return r;
+        }
+    }
+    HIPCHK(hipSetDevice(sc->device));
+    HIPCHK(hipDeviceSynchronize());  // launches that still read the old rule code
+    rules_release(&cp.rules);
+    cp.rules = dev;
+    cp.radix = choices;
+    sc->chain_keyspace = K;
+    if (keyspace) *keyspace = K;
+    return (int)nrules;
+}
+
 // No host synchronisation: the digits of `first` travel in the kernel arguments; the counter is zeroed on the stream
-// and counted up by the kernel, as in scan_load_hybrid.
+// and counted up by the kernel, as in scan_load_hybrid.  A chain with a ruled part launches k_prep_chain_rules, any
+// other k_prep_chain.
 int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen, void* stream) {
     if (!sc || !sc->chain_set || count > sc->batch_cap) return DWPA_E_ARG;
     const uint64_t K = sc->chain_keyspace;
@@ -1745,8 +1788,15 @@ int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minl
     uint64_t radix[CHAIN_MAX_PARTS], digit[CHAIN_MAX_PARTS];
     for (uint32_t p = 0; p < sc->chain_nparts; p++) radix[p] = sc->chain[p].radix;
     RCHK(chain_split(radix, sc->chain_nparts, first, digit));
+    bool ruled = false;
     for (uint32_t p = 0; p < sc->chain_nparts; p++) {
         const dwpa_scan::ChainPart& cp = sc->chain[p];
+        if (cp.rules.nrules) {
+            ruled = true;
+            lp[p].roffs = (const uint32_t*)cp.rules.offs;
+            lp[p].rcode = (const uint32_t*)cp.rules.code;
+            lp[p].nrules = cp.rules.nrules;
+        }
         lp[p].is_mask = cp.is_mask;
         lp[p].radix = cp.radix;
         lp[p].digit = digit[p];
@@ -1759,8 +1809,9 @@ int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minl
             lp[p].bytes = cp.bytes;
         }
     }
-    HIPCHK(launch_prep_chain(lp, sc->chain_nparts, first, count, minlen, maxlen, (uint32_t*)sc->batch.mid.p,
-                             (uint64_t*)sc->batch.ids.p, (uint32_t*)sc->batch.counters.p, sc->batch_cap, s));
+    HIPCHK((ruled ? launch_prep_chain_rules : launch_prep_chain)(
+        lp, sc->chain_nparts, first, count, minlen, maxlen, (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
+        (uint32_t*)sc->batch.counters.p, sc->batch_cap, s));
     return 0;
 }
 
@@ -2232,6 +2283,23 @@ int dwpa_scan_set_chain(dwpa_scan* scan, const dwpa_chain_part* parts, uint32_t 
             return DWPA_E_ARG;
         }
         return scan_set_chain(scan, parts, nparts, custom, keyspace);
+    });
+}
+int dwpa_scan_set_chain_rules(dwpa_scan* scan, uint32_t part, const char* rules_text, size_t rules_len,
+                              uint64_t* keyspace) {
+    return guarded([&]() -> int {
+        if (!scan) {
+            RCHK(ensure_init());
+            return DWPA_E_ARG;
+        }
+        if (!rules_text && rules_len) return DWPA_E_ARG;
+        // what is wrong with the call is said before what is wrong with the rules
+        if (!scan->chain_set || part >= scan->chain_nparts || scan->chain[part].is_mask) return DWPA_E_ARG;
+        if (rules_len == 0) return scan_set_chain_rules(scan, part, nullptr, keyspace);
+        RuleSet rs;  // rule text takes the whole language, as dwpa_scan_set_rules
+        rs.load_text(rules_text, rules_len);
+        if (rs.size() == 0) return DWPA_E_RULE;
+        return scan_set_chain_rules(scan, part, &rs, keyspace);
     });
 }
 int dwpa_scan_load_chain(dwpa_scan* scan, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen,

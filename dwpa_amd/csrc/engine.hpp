@@ -112,6 +112,10 @@ int scan_load_combinator(dwpa_scan* sc, const uint64_t* base_off, const uint8_t*
 // a chain of 1..4 lists and masks (chain_dev.hip); the lists' device pointers stay the caller's
 int scan_set_chain(dwpa_scan* sc, const dwpa_chain_part* parts, uint32_t nparts, const dwpa_bytes* custom,
                    uint64_t* keyspace);
+// rules on list part `part` of the chain (chain_rules_dev.hip); rs == nullptr takes them off.  Returns the number
+// of rules; *keyspace (nullable) = the new K.  A later scan_set_chain clears every part's rules.
+struct RuleSet;  // rules.hpp
+int scan_set_chain_rules(dwpa_scan* sc, uint32_t part, const RuleSet* rs, uint64_t* keyspace);
 int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen, void* stream);
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream);
 int scan_verify(dwpa_scan* sc, int group, void* stream);

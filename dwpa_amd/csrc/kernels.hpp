@@ -53,13 +53,24 @@ struct ChainPartLaunch {
     const uint8_t* bytes = nullptr;
     const uint8_t* table = nullptr;  // mask: the device copy of mask_table (mask.hpp)
     uint32_t npos = 0;               // mask: positions
-    uint64_t radix = 0;              // a list's word count (< 2^32), a mask's keyspace
+    uint64_t radix = 0;              // a list's word count (< 2^32), a mask's keyspace; a ruled list's nwords * nrules
     uint64_t digit = 0;              // digit of `first` at this part, < radix
     uint8_t digits[64] = {};         // mask: mask_digits of `digit`
+    // a ruled list (launch_prep_chain_rules only): the device image of its rule set (RuleSet::flatten); 0: no rules
+    const uint32_t* roffs = nullptr;
+    const uint32_t* rcode = nullptr;
+    uint32_t nrules = 0;
 };
 hipError_t launch_prep_chain(const ChainPartLaunch* parts, uint32_t nparts, uint64_t first, uint32_t count,
                              uint32_t minlen, uint32_t maxlen, uint32_t* mid, uint64_t* ids, uint32_t* counter,
                              uint32_t cap, hipStream_t s);
+// chain_rules_dev.hip: the same for a chain in which at least one list part carries rules: such a part's choices are
+// the (rule, word) pairs, rule-major (choice = rule * nwords + word, radix = nwords * nrules < 2^32), its piece is
+// rule_apply(word), and the <= 63 bytes test applies to that result; a choice the rule engine rejects drops the
+// candidate.  Un-ruled parts, the filter, the ids and the counter are launch_prep_chain's.
+hipError_t launch_prep_chain_rules(const ChainPartLaunch* parts, uint32_t nparts, uint64_t first, uint32_t count,
+                                   uint32_t minlen, uint32_t maxlen, uint32_t* mid, uint64_t* ids, uint32_t* counter,
+                                   uint32_t cap, hipStream_t s);
 // product launch: issue-pass code object (pbkdf2_module.cpp); DWPA_PBKDF2_PLAIN=1 -> launch_pbkdf2_plain
 // work (nullable): a 4-byte device counter the work-queue kernel may use (zeroed here before the launch)
 hipError_t launch_pbkdf2(const uint32_t* mid, uint32_t cap, uint32_t base, uint32_t count, const uint32_t* counter,

@@ -398,33 +398,67 @@ def chain_split(radices, index: int) -> list:
     return [int(d[i]) for i in range(n)]
 
 
-def chain_candidate(parts, index: int, custom=()) -> bytes:
+def chain_candidate(parts, index: int, custom=(), rules=None):
     """Candidate `index` of a chain (host only).  parts: one entry per part, a sequence of words (bytes) for a list
-    or ("mask", MASK) for a mask; the parts' choices at chain_split's digits, joined left to right.  Unfiltered."""
+    or ("mask", MASK) for a mask; the parts' choices at chain_split's digits, joined left to right.  Unfiltered.
+    rules: one entry per part, None or the rule text of a list part (the whole language; lines that do not parse are
+    skipped): that part's choices are then its (rule, word) pairs, rule-major -- digit = rule * len(words) + word --
+    and its piece is the rule applied by the GPU's interpreter on the host (dwpa_rules_apply_host).  Returns None when
+    a ruled part rejects its choice: an input word of 0 bytes or above 256, or a reject function."""
     parts = list(parts)
+    rules = [None] * len(parts) if rules is None else list(rules)
+    if len(rules) != len(parts):
+        raise L.DwpaError(L.DWPA_E_ARG, "chain_candidate takes one rules entry per part")
     masks = [isinstance(p, tuple) and len(p) == 2 and p[0] == "mask" for p in parts]
-    radices = [mask_keyspace(p[1], custom) if m else len(p) for p, m in zip(parts, masks)]
+    nrules = [None if r is None else rules_count(r)[1] for r in rules]
+    for m, n in zip(masks, nrules):
+        if n is not None and (m or n == 0):
+            raise L.DwpaError(L.DWPA_E_ARG if m else L.DWPA_E_RULE, "rules go with a list part and need a valid rule")
+    radices = [mask_keyspace(p[1], custom) if m else len(p) * (n or 1) for p, m, n in zip(parts, masks, nrules)]
     digits = chain_split(radices, index)
-    return b"".join(mask_candidate(p[1], d, custom) if m else _b(p[d]) for p, m, d in zip(parts, masks, digits))
+    out = []
+    for p, m, d, r in zip(parts, masks, digits, rules):
+        if m:
+            piece = mask_candidate(p[1], d, custom)
+        elif r is None:
+            piece = _b(p[d])
+        else:
+            piece = rules_apply_host(r, d // len(p), p[d % len(p)])
+            if piece is None:
+                return None
+        out.append(piece)
+    return b"".join(out)
 
 
 def crack_chain(hash_file, parts, custom=(), skip: int = 0, limit: int = 0, nonce_error_corrections: int = 8,
-                out_file="help_crack.key", device_mask: int = 0, batch: int = 0, nc_mode: int = L.DWPA_NC_HASHCAT):
+                out_file="help_crack.key", device_mask: int = 0, batch: int = 0, nc_mode: int = L.DWPA_NC_HASHCAT,
+                rules=None, rule_mode: int = L.DWPA_RULES_DEFAULT):
     """The chain attack over hash_file, on every selected device.  parts: 1..4 entries (DWPA_CHAIN_LIST, path of a
     plain or gzip word list) or (DWPA_CHAIN_MASK, mask); a candidate is one choice of every part joined left to right,
     candidate id = its index in itertools.product order.  skip / limit: raw indices [skip, skip + limit) (limit 0 = to
-    the end).  Returns (rc, part_status): a hashcat exit code (0 cracked, 1 exhausted, -1 error) and one status per
-    part (DWPA_DICT_OK | DWPA_DICT_DAMAGED | DWPA_E_IO)."""
+    the end).  rules: None, or one entry per part, each None or the path of a rules file for that list part
+    (dwpa_crack_chain_rules: the part's choices become its (rule, word) pairs, rule-major; the file loads under
+    rule_mode as crack_files' does).  Returns (rc, part_status): a hashcat exit code (0 cracked, 1 exhausted, -1
+    error) and one status per part (DWPA_DICT_OK | DWPA_DICT_DAMAGED | DWPA_E_IO)."""
     specs = [(int(k), _b(t)) for k, t in parts]
     for k, t in specs:
         if b"\0" in t:
             raise L.DwpaError(L.DWPA_E_ARG, "crack_chain takes NUL-terminated texts: put a NUL byte into a custom set")
     arr = (L.ChainSpec * max(1, len(specs)))(*[L.ChainSpec(k, t) for k, t in specs])
     carr, keep = _custom(custom)
-    cfg = L.Config(ctypes.sizeof(L.Config), device_mask, batch, nc_mode)
+    cfg = L.Config(ctypes.sizeof(L.Config), device_mask, batch, nc_mode, rule_mode)
     st = (ctypes.c_int32 * max(1, len(specs)))()
-    rc = L.load().dwpa_crack_chain(_b(hash_file), arr, len(specs), carr, _u64(skip, "skip"), _u64(limit, "limit"),
-                                   _nc(nonce_error_corrections), _b(out_file), ctypes.byref(cfg), st)
+    if rules is None:
+        rc = L.load().dwpa_crack_chain(_b(hash_file), arr, len(specs), carr, _u64(skip, "skip"), _u64(limit, "limit"),
+                                       _nc(nonce_error_corrections), _b(out_file), ctypes.byref(cfg), st)
+    else:
+        rl = [None if r is None else _b(r) for r in rules]
+        if len(rl) != len(specs):
+            raise L.DwpaError(L.DWPA_E_ARG, "crack_chain takes one rules entry per part")
+        rarr = (ctypes.c_char_p * max(1, len(rl)))(*rl)
+        rc = L.load().dwpa_crack_chain_rules(_b(hash_file), arr, len(specs), rarr, carr, _u64(skip, "skip"),
+                                             _u64(limit, "limit"), _nc(nonce_error_corrections), _b(out_file),
+                                             ctypes.byref(cfg), st)
     return rc, [int(st[i]) for i in range(len(specs))]
 
 
@@ -551,10 +585,25 @@ class Scan:
         self.chain_keyspace = k.value
         return k.value
 
+    def set_chain_rules(self, part: int, rules_text) -> int:
+        """Rules on list part `part` of the chain set by set_chain (rules_text: the whole rule language; empty takes
+        them off).  The part's choices become its (rule, word) pairs, rule-major: digit = rule * nwords + word, the
+        piece is rule(word), and the 63-byte limit applies to that result.  Returns the chain's new keyspace;
+        self.chain_nrules holds the number of rules parsed."""
+        t = _b(rules_text)
+        if not 0 <= int(part) < 2**32:
+            raise L.DwpaError(L.DWPA_E_ARG, f"part {part} is outside uint32")
+        k = ctypes.c_uint64(0)
+        self.chain_nrules = L.check(self._lib.dwpa_scan_set_chain_rules(self._h, int(part), t, len(t), ctypes.byref(k)),
+                                    "scan_set_chain_rules")
+        self.chain_keyspace = k.value
+        return k.value
+
     def load_chain(self, first: int, count: int, minlen=8, maxlen=63, stream: int = 0):
         """Raw chain candidates [first, first + count), generated and joined on the GPU.  A candidate is kept iff
-        every list word in it is at most 63 bytes and the total length is in minlen..maxlen; kept ones take compacted
-        slots in index order; candidate id = its raw index."""
+        every list word in it (for a ruled part: the rule's result) is at most 63 bytes, no ruled part rejects its
+        choice and the total length is in minlen..maxlen; kept ones take compacted slots in index order; candidate id
+        = its raw index."""
         for v, what in ((count, "count"), (minlen, "minlen"), (maxlen, "maxlen")):
             if not 0 <= int(v) < 2**32:
                 raise L.DwpaError(L.DWPA_E_ARG, f"{what} {v} is outside uint32")

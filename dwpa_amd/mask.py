@@ -42,7 +42,8 @@ def _parser() -> argparse.ArgumentParser:
                         "HASHFILE MASK DICT [DICT...]; 1 combinator: HASHFILE LEFT RIGHT")
     p.add_argument("--amplifier", default="right", metavar="SIDE",
                    help="-a 1: the list held whole in device memory, right (default) or left; the other is streamed")
-    p.add_argument("-j", "--rule-left", default=None, metavar="RULE", help="hashcat's -a 1 single rule: not supported")
+    p.add_argument("-j", "--rule-left", default=None, metavar="RULE", help="hashcat's -a 1 single rule: not supported here (python -m dwpa_amd.chain takes rule:TEXT "
+                        "after a list: part)")
     p.add_argument("-k", "--rule-right", default=None, metavar="RULE", help="hashcat's -a 1 single rule: not supported")
     for k in "1234":
         p.add_argument("-" + k, "--custom-charset" + k, dest="c" + k, metavar="CS", help="custom set ?" + k)
@@ -78,7 +79,8 @@ def main(argv=None) -> int:
     except SystemExit as e:  # argparse: 0 after --help, 2 for bad arguments
         return 0 if e.code in (0, None) else 255
     if a.rule_left is not None or a.rule_right is not None:
-        return _fail("the single rules -j / -k are not supported")
+        return _fail("the single rules -j / -k are not supported: python -m dwpa_amd.chain takes rule:TEXT or rules:FILE "
+                     "after a list: part")
     if a.attack_mode == 1:
         return _combinator(a)
     if a.attack_mode in (6, 7):

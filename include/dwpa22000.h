@@ -408,8 +408,21 @@ int dwpa_crack_combinator(const char *hash_file, const char *left_dict, const ch
  * crack call uses 8..63; a scan load treats maxlen above 64 as 64, one HMAC key block).  The decision is per
  * candidate.  An empty word is an ordinary word.  Dropped candidates leave no slots.  Two ids can be the same string;
  * both are candidates, and the crack call reports a line once, lowest id first.
- * Left out: streaming a list too big to hold, rules on parts, increment, and filling a batch from several raw
- * ranges -- a load is `batch` raw indices, so a chain whose filter drops most candidates runs short launches. */
+ * Rules on list parts (dwpa_scan_set_chain_rules, dwpa_crack_chain_rules) -- a list part may carry a rule set of
+ * R >= 1 parsed rules.  Its choices are then the (rule, word) pairs: N_p = nwords * R, which must stay below 2^32,
+ * ordered RULE-MAJOR with the word fastest: choice c = rule * nwords + word.  (This is not the word * nrules + rule id
+ * of the word list x rules attack: with the word fastest, 64 consecutive indices share one rule, or two at a wrap,
+ * whenever nwords >= 64, so the GPU's rule dispatch stays uniform across a wave.)  The piece is rule(word) by the
+ * interpreter of "hashcat rules" below: the input word is rejected at 0 bytes or above 256, reject and memory
+ * functions work as there, and a rejected choice drops the candidate.  A result of 0 bytes is an ordinary empty piece.
+ * For a ruled part the "<= 63 bytes" test applies to the RESULT: a 100-byte word under '8 is legal, a 40-byte word
+ * under d drops.  Un-ruled parts of the same chain are unchanged (an empty word is ordinary, a raw length above 63
+ * drops), and so are the order of the parts, id = raw index, the filter and K <= 2^64 - 1.  Rules *files* load under
+ * the process's rule mode as dwpa_crack_files' do (hashcat's -r loader unless DWPA_RULES_FULL), rule *text* takes the
+ * whole language; lines that do not parse are skipped with one stderr line each, a set with no valid rule is an error.
+ * Left out: streaming a list too big to hold, rules on mask parts or over the whole joined candidate, increment, and
+ * filling a batch from several raw ranges -- a load is `batch` raw indices, so a chain whose filter drops most
+ * candidates runs short launches. */
 #define DWPA_CHAIN_LIST 0
 #define DWPA_CHAIN_MASK 1
 #define DWPA_CHAIN_MAX_PARTS 4
@@ -438,6 +451,18 @@ typedef struct {
 int dwpa_crack_chain(const char *hash_file, const dwpa_chain_spec *parts, uint32_t nparts, const dwpa_bytes custom[4],
                      uint64_t skip, uint64_t limit, int nonce_error_corrections, const char *out_file,
                      const dwpa_config *cfg, int32_t *part_status /* nullable, nparts entries */);
+/* dwpa_crack_chain with rules on list parts ("Rules on list parts" above).  part_rules: nparts entries, each NULL
+ * (no rules) or the path of a rules file for that part; part_rules == NULL or every entry NULL is dwpa_crack_chain.
+ * A hit's PSK is rebuilt on the host from its id: the digits, a ruled part's digit split into (rule, word), the rule
+ * applied by the interpreter the GPU runs.  DWPA_RC_ERROR before any device is touched, besides dwpa_crack_chain's
+ * reasons: an unreadable rules file, a rules file with no valid rule, rules on a mask part, nwords * R >= 2^32.
+ * dwpa_crack_last_stats afterwards: rules, rules_skipped and rules_rejmem are sums over the parts; candidates = kept
+ * candidates derived. */
+int dwpa_crack_chain_rules(const char *hash_file, const dwpa_chain_spec *parts, uint32_t nparts,
+                           const char *const *part_rules /* nullable; nparts entries, NULL = no rules */,
+                           const dwpa_bytes custom[4], uint64_t skip, uint64_t limit, int nonce_error_corrections,
+                           const char *out_file, const dwpa_config *cfg,
+                           int32_t *part_status /* nullable, nparts entries */);
 
 /* hashcat rules (the whole rule language of hashcat >= 6.2.6: every mangling, reject and memory function; one
  * rule per line, '#' comments; semantics in dwpa_amd/csrc/rules.hpp and oracle/rules.py).  The text entry points
@@ -558,6 +583,16 @@ int dwpa_scan_set_chain(dwpa_scan *scan, const dwpa_chain_part *parts, uint32_t 
                         uint64_t *keyspace);
 int dwpa_scan_load_chain(dwpa_scan *scan, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen,
                          void *hip_stream);
+/* Rules on list part `part` of the chain set by dwpa_scan_set_chain ("Rules on list parts" above): rules_text is
+ * parsed as dwpa_scan_set_rules parses it (the whole language) and uploaded; rules_len == 0 takes the part's rules
+ * off.  K is recomputed and stored in *keyspace (nullable); dwpa_scan_load_chain then runs k_prep_chain_rules when
+ * any part is ruled and k_prep_chain otherwise.  Returns the number of rules parsed.  DWPA_E_ARG: no chain set, part
+ * out of range or a mask part, nwords * R >= 2^32, K above 2^64 - 1; DWPA_E_RULE: no rule parses.  A refused call
+ * leaves the scan usable with its previous chain and rules; every check is made before anything is read on the
+ * device, so an nwords that overstates the list is refused without touching it.  A later dwpa_scan_set_chain clears
+ * the rules of every part. */
+int dwpa_scan_set_chain_rules(dwpa_scan *scan, uint32_t part, const char *rules_text, size_t rules_len,
+                              uint64_t *keyspace /* nullable */);
 /* Stages 2 and 3 for ESSID group g (PMKs of the loaded batch, then every uncracked line of that ESSID). */
 int dwpa_scan_pbkdf2(dwpa_scan *scan, int group, void *hip_stream);
 int dwpa_scan_verify(dwpa_scan *scan, int group, void *hip_stream);
