@@ -9,6 +9,8 @@ this package is its Python host side:
 * :class:`Scan`            -- device-resident scan of HBM dictionaries / keyspaces (client hot loop, bench)
 * :func:`crack_mask`       -- hashcat ``-a 3`` mask attack (``python -m dwpa_amd.mask`` is its command line);
   :func:`mask_keyspace` / :func:`mask_candidate` are its host-only helpers
+  (``markov=`` / ``threshold=``: the Markov order under hashcat's ``-t``; :func:`markov_train` / :func:`markov_load`
+  make and read its model, ``python -m dwpa_amd.markov`` is their command line)
 * :func:`crack_hybrid`     -- hashcat ``-a 6`` / ``-a 7`` hybrid attacks, wordlist + mask and mask + wordlist
   (``python -m dwpa_amd.mask -a 6|7``); :meth:`Scan.load_hybrid` is their scan-path load
 * :func:`crack_combinator` -- hashcat ``-a 1`` combinator attack, word of one list + word of another
@@ -23,12 +25,12 @@ from ._lib import (DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS, DWPA_
                    DWPA_COMBI_AMP_RIGHT, DWPA_HYBRID_MASK_WORD, DWPA_HYBRID_WORD_MASK, DwpaError, load)
 from .m22000 import (BatchJobs, chain_candidate, chain_keyspace, chain_split, check_batch,  # noqa: F401
                      check_key_m22000, crack_chain, crack_combinator, crack_files, crack_hybrid, crack_mask,
-                     device_count, group_by_essid, mask_candidate, mask_keyspace, check_stats, hash_m22000, hc_unhex, init,
+                     device_count, group_by_essid, markov_load, markov_train, mask_candidate, mask_candidates, mask_keyspace, check_stats, hash_m22000, hc_unhex, init,
                      parse_m22000, pbkdf2_pmk, rules_count, rules_count_ex, rules_expand, Scan)
 
 __all__ = ["DwpaError", "load", "BatchJobs", "check_key_m22000", "check_batch", "pbkdf2_pmk", "hc_unhex", "hash_m22000",
            "crack_files", "rules_count", "rules_count_ex", "check_stats", "rules_expand", "device_count", "Scan",
-           "parse_m22000", "group_by_essid", "init", "crack_mask", "mask_keyspace", "mask_candidate",
+           "parse_m22000", "group_by_essid", "init", "crack_mask", "mask_keyspace", "mask_candidate", "mask_candidates", "markov_train", "markov_load",
            "crack_hybrid", "DWPA_HYBRID_WORD_MASK", "DWPA_HYBRID_MASK_WORD",
            "crack_combinator", "DWPA_COMBI_AMP_RIGHT", "DWPA_COMBI_AMP_LEFT",
            "crack_chain", "chain_keyspace", "chain_split", "chain_candidate", "DWPA_CHAIN_LIST", "DWPA_CHAIN_MASK",

@@ -23,6 +23,7 @@ DWPA_NC_MAX = 65664  # the largest nc / nonce_error_corrections taken (include/d
 DWPA_HYBRID_WORD_MASK, DWPA_HYBRID_MASK_WORD = 6, 7  # hashcat -a 6 (word || mask) / -a 7 (mask || word)
 DWPA_COMBI_AMP_RIGHT, DWPA_COMBI_AMP_LEFT = 0, 1  # hashcat -a 1: the list held whole in device memory
 DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS = 0, 1, 4  # chain attack: the kind of a part, the most parts
+DWPA_MARKOV_BYTES = 4128784  # a Markov model file / image: 16-byte header + 63 x 256 rows of 256 bytes
 DWPA_DICT_OK, DWPA_DICT_DAMAGED = 0, 1  # dwpa_crack_files_ex per-dictionary status (or DWPA_E_IO)
 DWPA_RULES_DEFAULT, DWPA_RULES_HASHCAT, DWPA_RULES_FULL = 0, 1, 2  # dwpa_config.rule_mode
 DWPA_BACKEND_DEVICE, DWPA_BACKEND_HOST_SMALL, DWPA_BACKEND_HOST_FALLBACK = 0, 1, 2  # dwpa_check_stats.backend
@@ -184,6 +185,23 @@ SIGNATURES = {
     "dwpa_crack_mask": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Bytes), ctypes.c_uint64, ctypes.c_uint64,
                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)],
                         ctypes.c_int),
+    "dwpa_markov_train": ([ctypes.POINTER(ctypes.c_char_p), ctypes.c_size_t, ctypes.c_char_p,
+                           ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_markov_load": ([ctypes.c_char_p, _P, ctypes.c_size_t], ctypes.c_int),
+    "dwpa_markov_check": ([ctypes.c_char_p, ctypes.c_size_t], ctypes.c_int),
+    "dwpa_mask_keyspace_markov": ([ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(Bytes), ctypes.c_uint32,
+                                   ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_mask_candidate_markov": ([ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(Bytes), ctypes.c_char_p,
+                                    ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64, _P,
+                                    ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+    "dwpa_mask_candidates_markov": ([ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(Bytes), ctypes.c_char_p,
+                                     ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t,
+                                     _P, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+    "dwpa_scan_set_mask_markov": ([_P, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(Bytes), ctypes.c_char_p,
+                                   ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_crack_mask_markov": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Bytes), ctypes.c_char_p,
+                                ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)], ctypes.c_int),
     "dwpa_scan_pbkdf2": ([_P, ctypes.c_int, _P], ctypes.c_int),
     "dwpa_scan_verify": ([_P, ctypes.c_int, _P], ctypes.c_int),
     "dwpa_scan_run": ([_P, _P], ctypes.c_int),

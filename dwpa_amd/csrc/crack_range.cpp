@@ -2,6 +2,8 @@
 // records, nc-mode default and cfg handling (crack_common.hpp):
 //   dwpa_crack_mask():  hashcat -a 3.  The keyspace is a list of segments, one per mask length that runs: the mask
 //                       itself, or with increment its prefixes, shortest first.
+//   dwpa_crack_mask_markov(): the same in Markov order under a threshold (markov.hpp): the segments index the
+//                       thresholded keyspace, and one model serves every prefix.
 //   dwpa_crack_chain(): a chain of 1..4 word lists and masks (chain.hpp).  Every list is read whole through the
 //                       dictionary reader once (plain or gzip, CRLF, $HEX[]), kept on the host to rebuild a hit's PSK
 //                       and uploaded once per worker.  The keyspace is one segment of raw indices [skip, skip + limit).
@@ -37,6 +39,7 @@
 #include "crack_common.hpp"
 #include "crack_cursor.hpp"
 #include "engine.hpp"
+#include "markov.hpp"
 #include "mask.hpp"
 #include "rules.hpp"
 
@@ -134,6 +137,44 @@ struct MaskAttack {
     };
 };
 
+// The segments of a mask run: the mask itself over [skip, skip + limit), or with increment its prefixes of inc_min..
+// inc_max positions, shortest first.  npos: the mask's positions, keyspace_of(n): the keyspace of its first n.  Fills
+// npos_of (the positions of each segment's prefix) and segs; false after a message for what hashcat refuses.  Both
+// empty: nothing is left to run.
+template <class KeyspaceOf>
+bool mask_segments(const char* mask, uint32_t npos, KeyspaceOf keyspace_of, uint64_t skip, uint64_t limit,
+                   uint32_t inc_min, uint32_t inc_max, std::vector<uint32_t>* npos_of, std::vector<RangeSegment>* segs) {
+    const bool increment = inc_min || inc_max;
+    if (increment && (skip || limit)) {
+        fprintf(stderr, "[dwpa] --increment cannot be combined with --skip / --limit\n");
+        return false;
+    }
+    if (increment) {
+        const uint32_t lo = std::max<uint32_t>(1, inc_min), hi = std::min(inc_max ? inc_max : npos, npos);
+        if (lo > hi) return false;
+        for (uint32_t n = lo; n <= hi; n++) {
+            if (n < 8) {  // hashcat skips a mask shorter than the hash mode's shortest password
+                fprintf(stderr, "[dwpa] skipping the mask's first %u positions: m22000 takes 8..63 characters\n", n);
+                continue;
+            }
+            npos_of->push_back(n);
+            segs->push_back(RangeSegment{0, keyspace_of(n)});
+        }
+    } else if (npos < 8) {
+        fprintf(stderr, "[dwpa] skipping mask %s: %u positions, m22000 takes 8..63 characters\n", mask, npos);
+    } else {
+        const uint64_t K = keyspace_of(npos);
+        if (skip >= K) {
+            fprintf(stderr, "[dwpa] --skip is not below the keyspace\n");
+            return false;
+        }
+        const uint64_t room = K - skip;
+        npos_of->push_back(npos);
+        segs->push_back(RangeSegment{skip, skip + (limit && limit < room ? limit : room)});
+    }
+    return true;
+}
+
 int crack_mask_impl(const char* hash_file, const char* mask, const dwpa_bytes* custom, uint64_t skip, uint64_t limit,
                     uint32_t inc_min, uint32_t inc_max, int nec, const char* out_file, const dwpa_config* cfg) {
     CrackCall call;
@@ -145,37 +186,79 @@ int crack_mask_impl(const char* hash_file, const char* mask, const dwpa_bytes* c
                         "above 2^64 - 1)\n", mask);
         return DWPA_RC_ERROR;
     }
-    const bool increment = inc_min || inc_max;
-    if (increment && (skip || limit)) {
-        fprintf(stderr, "[dwpa] --increment cannot be combined with --skip / --limit\n");
-        return DWPA_RC_ERROR;
-    }
     MaskAttack attack{*full, {}};
     std::vector<RangeSegment> segs;
-    if (increment) {
-        const uint32_t lo = std::max<uint32_t>(1, inc_min), hi = std::min(inc_max ? inc_max : full->npos, full->npos);
-        if (lo > hi) return DWPA_RC_ERROR;
-        auto pre = std::make_unique<Mask>();
-        for (uint32_t n = lo; n <= hi; n++) {
-            if (n < 8) {  // hashcat skips a mask shorter than the hash mode's shortest password
-                fprintf(stderr, "[dwpa] skipping the mask's first %u positions: m22000 takes 8..63 characters\n", n);
-                continue;
-            }
+    auto pre = std::make_unique<Mask>();
+    if (!mask_segments(mask, full->npos, [&](uint32_t n) {
             mask_prefix(*full, n, pre.get());
-            attack.npos.push_back(n);
-            segs.push_back(RangeSegment{0, pre->keyspace});
+            return pre->keyspace;
+        }, skip, limit, inc_min, inc_max, &attack.npos, &segs))
+        return DWPA_RC_ERROR;
+    if (segs.empty()) return DWPA_RC_ERROR;  // nothing left to run
+    return crack_range(call, hash_file, nec, out_file, cfg, std::move(segs), attack);
+}
+
+struct MarkovAttack {
+    const MarkovMask& full;
+    const std::vector<uint8_t>& model;
+    std::vector<uint32_t> npos;  // per segment: the positions of its prefix
+
+    struct Worker {
+        const MarkovAttack& at;
+        std::unique_ptr<MarkovMask> cur = std::make_unique<MarkovMask>();  // the prefix this worker's scan holds
+        explicit Worker(const MarkovAttack& a) : at(a) {}
+        int open(ScanWorker&) { return 0; }
+        int enter(ScanWorker& w, size_t seg) {
+            markov_prefix(at.full, at.npos[seg], cur.get());
+            return scan_set_mask_markov(w.scan, *cur, at.model.data());
         }
-    } else if (full->npos < 8) {
-        fprintf(stderr, "[dwpa] skipping mask %s: %u positions, m22000 takes 8..63 characters\n", mask, full->npos);
-    } else {
-        if (skip >= full->keyspace) {
-            fprintf(stderr, "[dwpa] --skip is not below the keyspace\n");
-            return DWPA_RC_ERROR;
+        int load(ScanWorker& w, uint64_t first, uint32_t count) { return scan_load_mask(w.scan, first, count, w.stream); }
+        int counted(ScanWorker&, uint32_t count, uint64_t* n) {
+            *n = count;  // every index is a candidate: nothing to read back
+            return 0;
         }
-        const uint64_t room = full->keyspace - skip;
-        attack.npos.push_back(full->npos);
-        segs.push_back(RangeSegment{skip, skip + (limit && limit < room ? limit : room)});
+        bool plain_of(uint64_t id, std::string* psk) const {
+            if (id >= cur->keyspace) return false;
+            uint8_t m[64];
+            markov_candidate(*cur, at.model.data(), id, m);
+            psk->assign((const char*)m, cur->npos);
+            return true;
+        }
+    };
+};
+
+int crack_mask_markov_impl(const char* hash_file, const char* mask, const dwpa_bytes* custom, const char* markov_file,
+                           uint32_t threshold, uint64_t skip, uint64_t limit, uint32_t inc_min, uint32_t inc_max,
+                           int nec, const char* out_file, const dwpa_config* cfg) {
+    CrackCall call;
+    if (!hash_file || !mask || !markov_file || !out_file) return DWPA_RC_ERROR;
+    if (!crack_check_args(cfg, nec)) return DWPA_RC_ERROR;
+    auto sets = std::make_unique<Mask>();
+    auto full = std::make_unique<MarkovMask>();
+    if (threshold > 256) {
+        fprintf(stderr, "[dwpa] the Markov threshold takes 0 (none) or 1..256\n");
+        return DWPA_RC_ERROR;
     }
+    if (mask_parse_sets(mask, strlen(mask), custom, sets.get()) < 0 || markov_mask(*sets, threshold, full.get()) < 0) {
+        fprintf(stderr, "[dwpa] mask %s: invalid (syntax, an undefined custom set, more than 63 positions or a keyspace "
+                        "above 2^64 - 1)\n", mask);
+        return DWPA_RC_ERROR;
+    }
+    std::vector<uint8_t> model;
+    const int mr = markov_read_file(markov_file, &model);
+    if (mr < 0) {
+        fprintf(stderr, "[dwpa] Markov model %s: %s\n", markov_file,
+                mr == DWPA_E_IO ? "cannot be read" : "not a model file (size, header or a row that is no permutation)");
+        return DWPA_RC_ERROR;
+    }
+    MarkovAttack attack{*full, model, {}};
+    std::vector<RangeSegment> segs;
+    auto pre = std::make_unique<MarkovMask>();
+    if (!mask_segments(mask, full->npos, [&](uint32_t n) {
+            markov_prefix(*full, n, pre.get());
+            return pre->keyspace;
+        }, skip, limit, inc_min, inc_max, &attack.npos, &segs))
+        return DWPA_RC_ERROR;
     if (segs.empty()) return DWPA_RC_ERROR;  // nothing left to run
     return crack_range(call, hash_file, nec, out_file, cfg, std::move(segs), attack);
 }
@@ -397,6 +480,16 @@ extern "C" int dwpa_crack_mask(const char* hash_file, const char* mask, const dw
     return dwpa::guarded([&]() -> int {
         return dwpa::crack_mask_impl(hash_file, mask, custom, skip, limit, increment_min, increment_max,
                                      nonce_error_corrections, out_file, cfg);
+    }, DWPA_RC_ERROR, DWPA_RC_ERROR);
+}
+
+extern "C" int dwpa_crack_mask_markov(const char* hash_file, const char* mask, const dwpa_bytes custom[4],
+                                      const char* markov_file, uint32_t threshold, uint64_t skip, uint64_t limit,
+                                      uint32_t increment_min, uint32_t increment_max, int nonce_error_corrections,
+                                      const char* out_file, const dwpa_config* cfg) {
+    return dwpa::guarded([&]() -> int {
+        return dwpa::crack_mask_markov_impl(hash_file, mask, custom, markov_file, threshold, skip, limit, increment_min,
+                                            increment_max, nonce_error_corrections, out_file, cfg);
     }, DWPA_RC_ERROR, DWPA_RC_ERROR);
 }
 

@@ -33,6 +33,7 @@
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "m22000_host.hpp"
+#include "markov.hpp"
 #include "mask.hpp"
 #include "chain.hpp"
 #include "rules.hpp"
@@ -1485,6 +1486,11 @@ struct dwpa_scan {
     bool mask_set = false;
     dwpa::Mask mask;
     dwpa::DevBuf mask_tab;
+    // dwpa_scan_set_mask_markov: the thresholded mask (host copy, for the digits of `first`) and its device table
+    // (markov.hpp markov_table).  At most one of mask_set / markov_set holds: the set call of one kind drops the other.
+    bool markov_set = false;
+    std::unique_ptr<dwpa::MarkovMask> markov;
+    dwpa::DevBuf markov_tab;
     // dwpa_scan_set_chain: the parts as given (the lists' device pointers are the caller's), the parsed mask of every
     // mask part (host copy: dwpa_scan_load_chain decomposes `first` with it) and one device table each; mask_tab is not
     // touched.  dwpa_scan_set_chain_rules: a list part's rule set on the device; its radix is then nwords * nrules.
@@ -1571,6 +1577,7 @@ void scan_destroy(dwpa_scan* sc) {
     sc->lines.release(); sc->atts.release(); sc->pool.release(); sc->salt.release(); sc->segs.release();
     sc->mg_pmk.release(); sc->mg_gsalt.release(); sc->mg_list.release(); sc->mg_poff.release();
     sc->mask_tab.release();
+    sc->markov_tab.release();
     for (auto& cp : sc->chain) {
         cp.tab.release();
         rules_release(&cp.rules);
@@ -1618,6 +1625,7 @@ int scan_set_mask(dwpa_scan* sc, const Mask& m) {
     mask_table(m, tab.data());
     HIPCHK(hipDeviceSynchronize());
     sc->mask_set = false;
+    sc->markov_set = false;
     RCHK(sc->mask_tab.ensure(MASK_TABLE_BYTES));
     HIPCHK(hipMemcpy(sc->mask_tab.p, tab.data(), MASK_TABLE_BYTES, hipMemcpyHostToDevice));
     sc->mask = m;
@@ -1625,8 +1633,40 @@ int scan_set_mask(dwpa_scan* sc, const Mask& m) {
     return 0;
 }
 
+// As scan_set_mask: launches that still read the old table are waited for first.
+int scan_set_mask_markov(dwpa_scan* sc, const MarkovMask& mm, const uint8_t* model) {
+    if (!sc || !model || mm.npos == 0 || mm.npos > MARKOV_POS) return DWPA_E_ARG;
+    HIPCHK(hipSetDevice(sc->device));
+    const size_t bytes = markov_table_bytes(mm.npos);
+    std::vector<uint8_t> tab(bytes, 0);
+    markov_table(mm, model, tab.data());
+    HIPCHK(hipDeviceSynchronize());
+    sc->mask_set = false;
+    sc->markov_set = false;
+    RCHK(sc->markov_tab.ensure(bytes));
+    HIPCHK(hipMemcpy(sc->markov_tab.p, tab.data(), bytes, hipMemcpyHostToDevice));
+    if (!sc->markov) sc->markov = std::make_unique<MarkovMask>();
+    *sc->markov = mm;
+    sc->markov_set = true;
+    return 0;
+}
+
+static int scan_load_markov(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream) {
+    if (count > sc->batch_cap) return DWPA_E_ARG;
+    const uint64_t K = sc->markov->keyspace;
+    if (first > K || count > K - first) return DWPA_E_ARG;  // first + count > K, also when the sum wraps
+    HIPCHK(hipSetDevice(sc->device));
+    uint8_t digits[64];
+    markov_digits(*sc->markov, first < K ? first : 0, digits);  // first == K only with count 0
+    HIPCHK(launch_prep_markov(digits, first, count, sc->markov->npos, (const uint8_t*)sc->markov_tab.p,
+                              (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
+                              (uint32_t*)sc->batch.counters.p, sc->batch_cap, as_stream(stream)));
+    return 0;
+}
+
 // No host synchronisation: the digits of `first` travel in the kernel arguments and the kernel writes the loaded count.
 int scan_load_mask(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream) {
+    if (sc && sc->markov_set) return scan_load_markov(sc, first, count, stream);
     if (!sc || !sc->mask_set || count > sc->batch_cap) return DWPA_E_ARG;
     const uint64_t K = sc->mask.keyspace;
     if (first > K || count > K - first) return DWPA_E_ARG;  // first + count > K, also when the sum wraps
@@ -2247,6 +2287,23 @@ int dwpa_scan_set_mask(dwpa_scan* scan, const char* mask, size_t mask_len, const
         RCHK(mask_parse(mask, mask_len, custom, &m));
         RCHK(scan_set_mask(scan, m));
         if (keyspace) *keyspace = m.keyspace;
+        return 0;
+    });
+}
+int dwpa_scan_set_mask_markov(dwpa_scan* scan, const char* mask, size_t mask_len, const dwpa_bytes custom[4],
+                              const uint8_t* model, size_t model_len, uint32_t threshold, uint64_t* keyspace) {
+    return guarded([&]() -> int {
+        if (!scan) {  // no scan can exist without a device: say so first
+            RCHK(ensure_init());
+            return DWPA_E_ARG;
+        }
+        auto sets = std::make_unique<Mask>();
+        auto mm = std::make_unique<MarkovMask>();
+        RCHK(mask_parse_sets(mask, mask_len, custom, sets.get()));
+        RCHK(markov_mask(*sets, threshold, mm.get()));
+        RCHK(markov_validate(model, model_len));
+        RCHK(scan_set_mask_markov(scan, *mm, model));
+        if (keyspace) *keyspace = mm->keyspace;
         return 0;
     });
 }

@@ -98,6 +98,10 @@ int scan_load_dict(dwpa_scan* sc, const uint64_t* off, const uint8_t* bytes, uin
 int scan_load_numeric(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t digits, void* stream);
 struct Mask;  // mask.hpp
 int scan_set_mask(dwpa_scan* sc, const Mask& m);
+// The scan's mask in Markov order (markov_dev.hip): replaces a mask of either kind, and scan_set_mask replaces it;
+// scan_load_mask launches the kernel of whichever was set last.  model: a validated image.
+struct MarkovMask;  // markov.hpp
+int scan_set_mask_markov(dwpa_scan* sc, const MarkovMask& mm, const uint8_t* model);
 int scan_load_mask(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream);
 // fill = true (crack_hybrid): nwords * mask_count may reach 16 batches (below 2^32), as for scan_load_dict
 int scan_load_hybrid(dwpa_scan* sc, const uint64_t* off, const uint8_t* bytes, uint64_t first_word, uint32_t nwords,

@@ -23,6 +23,11 @@ hipError_t launch_prep_numeric(uint64_t first, uint32_t count, uint32_t digits, 
 hipError_t launch_prep_mask(const uint8_t digits[64], uint64_t first, uint32_t count, uint32_t npos,
                             const uint8_t* table, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
                             hipStream_t s);
+// markov_dev.hip: the same for the Markov-ordered mask (markov.hpp): digits over the thresholded radices
+// (markov_digits), table: the device copy of markov_table.
+hipError_t launch_prep_markov(const uint8_t digits[64], uint64_t first, uint32_t count, uint32_t npos,
+                              const uint8_t* table, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
+                              hipStream_t s);
 // hybrid_dev.hip: words [first_word, first_word + nwords) of off/bytes x mask candidates [mask_first, mask_first +
 // mask_count), word-major, joined as word || mask or (mask_then_word) mask || word -> midstates in compacted slots;
 // kept iff len <= 63 and minlen <= len + npos <= min(maxlen, 64); ids[slot] = word * keyspace + mask index.  The

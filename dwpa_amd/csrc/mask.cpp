@@ -61,7 +61,7 @@ size_t take(const uint8_t* p, size_t i, size_t len, const Set* custom, const boo
 
 }  // namespace
 
-int mask_parse(const char* mask, size_t len, const dwpa_bytes* custom_in, Mask* out) {
+int mask_parse_sets(const char* mask, size_t len, const dwpa_bytes* custom_in, Mask* out) {
     if (!mask || !out || len == 0) return DWPA_E_ARG;
     Set custom[4];
     bool defined[4] = {false, false, false, false};
@@ -78,7 +78,7 @@ int mask_parse(const char* mask, size_t len, const dwpa_bytes* custom_in, Mask* 
         defined[k] = true;
     }
     out->npos = 0;
-    out->keyspace = 1;
+    out->keyspace = 0;
     const uint8_t* p = (const uint8_t*)mask;
     for (size_t i = 0; i < len;) {
         if (out->npos == MASK_MAX_POS) return DWPA_E_ARG;
@@ -89,10 +89,20 @@ int mask_parse(const char* mask, size_t len, const dwpa_bytes* custom_in, Mask* 
         MaskPos& mp = out->pos[out->npos++];
         mp.radix = s.n;
         memcpy(mp.bytes, s.b, 256);
-        if (out->keyspace > UINT64_MAX / s.n) return DWPA_E_ARG;  // K above 2^64 - 1
-        out->keyspace *= s.n;
     }
     return out->npos ? 0 : DWPA_E_ARG;
+}
+
+int mask_parse(const char* mask, size_t len, const dwpa_bytes* custom_in, Mask* out) {
+    const int r = mask_parse_sets(mask, len, custom_in, out);
+    if (r < 0) return r;
+    out->keyspace = 1;
+    for (uint32_t p = 0; p < out->npos; p++) {
+        const uint32_t n = out->pos[p].radix;
+        if (out->keyspace > UINT64_MAX / n) return DWPA_E_ARG;  // K above 2^64 - 1
+        out->keyspace *= n;
+    }
+    return 0;
 }
 
 void mask_prefix(const Mask& m, uint32_t n, Mask* out) {

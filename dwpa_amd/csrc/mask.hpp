@@ -37,6 +37,9 @@ struct Mask {
 // not lower-numbered custom set, an empty set, no position or more than 63, a keyspace above 2^64 - 1.  Every defined
 // custom set is expanded, referenced or not (hashcat parses -1..-4 at start-up).
 int mask_parse(const char* mask, size_t len, const dwpa_bytes* custom, Mask* out);
+// The same without the keyspace test: the positions' sets alone, keyspace left 0 (markov.hpp cuts the sets down by a
+// threshold before it multiplies them).
+int mask_parse_sets(const char* mask, size_t len, const dwpa_bytes* custom, Mask* out);
 // The first n positions of m as a mask of their own (1 <= n <= m.npos; the product of fewer radices cannot overflow).
 void mask_prefix(const Mask& m, uint32_t n, Mask* out);
 // Candidate `index` (< keyspace) into out[0..npos).

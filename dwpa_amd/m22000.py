@@ -9,6 +9,7 @@ asked for, ``init(allow_cpu_fallback=1)``) without a device; otherwise a call wi
 from __future__ import annotations
 
 import ctypes
+import os
 
 from . import _lib as L
 
@@ -291,28 +292,76 @@ def _u64(v, what) -> int:
     return v
 
 
-def mask_keyspace(mask, custom=()) -> int:
+def markov_train(dicts, out_file) -> int:
+    """Train a Markov model (include/dwpa22000.h "mask attack in Markov order") from word lists, plain or gzip, read
+    as every attack reads them, and write it to out_file; returns the number of words that contributed.  Raises
+    DwpaError(DWPA_E_IO) for an unreadable list or a damaged gzip stream (no file is written then)."""
+    paths = [_b(d) for d in ([dicts] if isinstance(dicts, (str, bytes, os.PathLike)) else dicts)]
+    arr = (ctypes.c_char_p * max(1, len(paths)))(*paths)
+    words = ctypes.c_uint64(0)
+    L.check(L.load().dwpa_markov_train(arr, len(paths), _b(out_file), ctypes.byref(words)), "markov_train")
+    return words.value
+
+
+def markov_load(path) -> bytes:
+    """The Markov model file at `path` as a validated image (DWPA_MARKOV_BYTES bytes).  Raises DwpaError: DWPA_E_IO
+    unreadable, DWPA_E_ARG another size, another header or a row that is no permutation of 0..255."""
+    out = ctypes.create_string_buffer(L.DWPA_MARKOV_BYTES)
+    L.check(L.load().dwpa_markov_load(_b(path), out, L.DWPA_MARKOV_BYTES), "markov_load")
+    return out.raw
+
+
+def _threshold(threshold) -> int:
+    t = int(threshold)
+    if not 0 <= t <= 256:
+        raise L.DwpaError(L.DWPA_E_ARG, f"threshold {t}: 0 (none) or 1..256")
+    return t
+
+
+def _model(markov, threshold) -> bytes:
+    if markov is None:
+        raise L.DwpaError(L.DWPA_E_ARG, f"threshold {threshold} needs a Markov model (markov_train / markov_load): "
+                                        "there are no built-in statistics")
+    return bytes(markov)
+
+
+def mask_keyspace(mask, custom=(), threshold: int = 0) -> int:
     """Keyspace of a hashcat -a 3 mask (host only): the product of its positions' set sizes.  custom: the sets
-    ?1..?4 as raw bytes in the mask language.  Raises DwpaError(DWPA_E_ARG) for an invalid mask or K > 2**64 - 1."""
+    ?1..?4 as raw bytes in the mask language.  threshold (hashcat -t, 1..256; 0 = none): every position cut down to
+    that many bytes at most; needs no model.  Raises DwpaError(DWPA_E_ARG) for an invalid mask or K > 2**64 - 1."""
     m = _b(mask)
     arr, keep = _custom(custom)
     k = ctypes.c_uint64(0)
+    if threshold:
+        L.check(L.load().dwpa_mask_keyspace_markov(m, len(m), arr, _threshold(threshold), None, ctypes.byref(k)),
+                "mask_keyspace_markov")
+        return k.value
     L.check(L.load().dwpa_mask_keyspace(m, len(m), arr, None, ctypes.byref(k)), "mask_keyspace")
     return k.value
 
 
-def mask_positions(mask, custom=()) -> int:
-    """Positions (candidate length) of a mask (host only)."""
+def mask_positions(mask, custom=(), threshold: int = 0) -> int:
+    """Positions (candidate length) of a mask (host only); threshold as for mask_keyspace (a mask whose keyspace
+    only fits under the threshold is valid only with it)."""
     m = _b(mask)
     arr, keep = _custom(custom)
     n = ctypes.c_uint32(0)
+    if threshold:
+        L.check(L.load().dwpa_mask_keyspace_markov(m, len(m), arr, _threshold(threshold), ctypes.byref(n), None),
+                "mask_keyspace_markov")
+        return n.value
     L.check(L.load().dwpa_mask_keyspace(m, len(m), arr, ctypes.byref(n), None), "mask_keyspace")
     return n.value
 
 
-def mask_candidate(mask, index: int, custom=()) -> bytes:
+def mask_candidate(mask, index: int, custom=(), markov=None, threshold: int = 0) -> bytes:
     """Candidate `index` of a mask (host only), in the library's order: the mixed-radix numeral of the index with the
-    last position fastest (itertools.product order; hashcat's own order differs, the candidate set does not)."""
+    last position fastest (itertools.product order; hashcat's own order differs, the candidate set does not).
+    markov (a model image, markov_load) / threshold: the candidate of the Markov order instead, each digit choosing
+    from the model's ranking after the byte before it; the image is validated on every call (mask_candidates takes
+    many indices at once)."""
+    if markov is not None or threshold:
+        return mask_candidates(mask, [index], custom, markov, threshold)[0]
     m = _b(mask)
     arr, keep = _custom(custom)
     out = ctypes.create_string_buffer(64)
@@ -321,13 +370,28 @@ def mask_candidate(mask, index: int, custom=()) -> bytes:
     return out.raw[:n.value]
 
 
+def mask_candidates(mask, indices, custom=(), markov=None, threshold: int = 0) -> list:
+    """The Markov-order candidates (host only) of `indices` under a model image and a threshold, in one call."""
+    m = _b(mask)
+    arr, keep = _custom(custom)
+    model = _model(markov, threshold)
+    idx = [_u64(i, "index") for i in indices]
+    ia = (ctypes.c_uint64 * max(1, len(idx)))(*idx)
+    out = ctypes.create_string_buffer(64 * max(1, len(idx)))
+    n = ctypes.c_uint32(0)
+    L.check(L.load().dwpa_mask_candidates_markov(m, len(m), arr, model, len(model), _threshold(threshold), ia, len(idx),
+                                                 out, ctypes.byref(n)), "mask_candidates_markov")
+    return [out.raw[64 * k:64 * k + n.value] for k in range(len(idx))]
+
+
 def crack_mask(hash_file, mask, custom=(), skip: int = 0, limit: int = 0, increment=None,
                nonce_error_corrections: int = 8, out_file="help_crack.key", device_mask: int = 0, batch: int = 0,
-               nc_mode: int = L.DWPA_NC_HASHCAT) -> int:
+               nc_mode: int = L.DWPA_NC_HASHCAT, markov=None, threshold: int = 0) -> int:
     """In-process `hashcat -m22000 -a 3 hash_file mask`; returns a hashcat exit code (0 cracked, 1 exhausted,
     -1 error).  skip / limit: indices [skip, skip + limit) of the keyspace in the library's order (limit 0 = to the
     end).  increment: None = off, else (min, max) = the mask's prefixes of min..max positions, shortest first (not
-    with skip / limit).  Runs on every selected device."""
+    with skip / limit).  Runs on every selected device.  markov (the PATH of a model file, markov_train) / threshold
+    (hashcat -t): the Markov order under that threshold instead; skip / limit then index the thresholded keyspace."""
     m = _b(mask)
     if b"\0" in m:
         raise L.DwpaError(L.DWPA_E_ARG, "crack_mask takes a NUL-terminated mask: put a NUL byte into a custom set")
@@ -336,6 +400,12 @@ def crack_mask(hash_file, mask, custom=(), skip: int = 0, limit: int = 0, increm
     if increment is not None and not (imin or imax):
         imin = 1  # (0, 0) would mean "off" in the C call
     cfg = L.Config(ctypes.sizeof(L.Config), device_mask, batch, nc_mode)
+    if markov is not None or threshold:
+        if markov is None:
+            _model(markov, threshold)
+        return L.load().dwpa_crack_mask_markov(_b(hash_file), m, arr, _b(markov), _threshold(threshold),
+                                               _u64(skip, "skip"), _u64(limit, "limit"), imin, imax,
+                                               _nc(nonce_error_corrections), _b(out_file), ctypes.byref(cfg))
     return L.load().dwpa_crack_mask(_b(hash_file), m, arr, _u64(skip, "skip"), _u64(limit, "limit"), imin, imax,
                                     _nc(nonce_error_corrections), _b(out_file), ctypes.byref(cfg))
 
@@ -522,11 +592,19 @@ class Scan:
     def load_numeric(self, first: int, count: int, digits: int = 8, stream: int = 0):
         L.check(self._lib.dwpa_scan_load_numeric(self._h, first, count, digits, stream), "scan_load_numeric")
 
-    def set_mask(self, mask, custom=()) -> int:
-        """Set the scan's hashcat -a 3 mask (custom: the sets ?1..?4 as raw bytes); returns its keyspace."""
+    def set_mask(self, mask, custom=(), markov=None, threshold: int = 0) -> int:
+        """Set the scan's hashcat -a 3 mask (custom: the sets ?1..?4 as raw bytes); returns its keyspace.  markov (a
+        model image, markov_load) / threshold: the mask in Markov order under that threshold; load_mask then
+        generates that order's candidates, and the keyspace returned is the thresholded one."""
         m = _b(mask)
         arr, keep = _custom(custom)
         k = ctypes.c_uint64(0)
+        if markov is not None or threshold:
+            model = _model(markov, threshold)
+            L.check(self._lib.dwpa_scan_set_mask_markov(self._h, m, len(m), arr, model, len(model),
+                                                        _threshold(threshold), ctypes.byref(k)), "scan_set_mask_markov")
+            self.keyspace = k.value
+            return k.value
         L.check(self._lib.dwpa_scan_set_mask(self._h, m, len(m), arr, ctypes.byref(k)), "scan_set_mask")
         self.keyspace = k.value
         return k.value

@@ -19,6 +19,12 @@ too big to hold.  The candidates are the same, their order differs: the streamed
 
 The candidates of a mask are hashcat's; their ORDER is the library's own (last position fastest, Python's
 ``itertools.product`` order), so ``-s`` / ``-l`` windows do not name the candidates hashcat's windows name.
+
+``--markov FILE`` walks an ``-a 3`` mask in Markov order instead: every digit chooses from the model's ranking of the
+bytes that follow the byte before it, most likely first, and ``-t / --markov-threshold N`` cuts every position down to
+its N most likely bytes.  ``-i``, ``-s`` / ``-l`` (over the thresholded keyspace), ``--keyspace`` (with ``-t`` it needs
+no model) and ``--stdout`` follow.  FILE comes from ``python -m dwpa_amd.markov train``: there are no built-in
+statistics and hashcat's ``hashcat.hcstat2`` is not read, so this order is the library's own as well.
 """
 from __future__ import annotations
 
@@ -57,6 +63,11 @@ def _parser() -> argparse.ArgumentParser:
     p.add_argument("-o", "--outfile", default="help_crack.key")
     p.add_argument("--nonce-error-corrections", type=int, default=8, metavar="N")
     p.add_argument("--batch", type=int, default=0, help="candidate slots per launch (0: the library's default)")
+    p.add_argument("--markov", default=None, metavar="FILE",
+                   help="-a 3: walk the mask in Markov order by this model (python -m dwpa_amd.markov train)")
+    p.add_argument("-t", "--markov-threshold", type=int, default=None, metavar="N", dest="threshold",
+                   help="-a 3: cut every position down to its N most likely bytes (1..256); needs --markov, except "
+                        "with --keyspace")
     p.add_argument("--keyspace", action="store_true",
                    help="print the mask's whole keyspace (the number of candidates) and exit.  hashcat prints a "
                         "reduced figure for -a 3: the count its host loop steps through, without the part its "
@@ -81,6 +92,10 @@ def main(argv=None) -> int:
     if a.rule_left is not None or a.rule_right is not None:
         return _fail("the single rules -j / -k are not supported: python -m dwpa_amd.chain takes rule:TEXT or rules:FILE "
                      "after a list: part")
+    if a.attack_mode in (1, 6, 7) and (a.markov is not None or a.threshold is not None):
+        return _fail(f"--markov / -t belong to -a 3: not available with -a {a.attack_mode}")
+    if a.threshold is not None and not 1 <= a.threshold <= 256:
+        return _fail("-t takes 1..256")
     if a.attack_mode == 1:
         return _combinator(a)
     if a.attack_mode in (6, 7):
@@ -105,9 +120,13 @@ def main(argv=None) -> int:
         return _fail("--increment-min is above --increment-max")
     if increment and (a.skip or a.limit):
         return _fail("--increment cannot be combined with --skip / --limit")
+    t = a.threshold or 0
+    if t and a.markov is None and not a.keyspace:
+        return _fail("-t needs --markov FILE: there are no built-in statistics; train a model with "
+                     "python -m dwpa_amd.markov train OUT.dwmk DICT [DICT ...]")
     try:
-        npos = M.mask_positions(mask, custom)
-        keyspace = M.mask_keyspace(mask, custom)
+        npos = M.mask_positions(mask, custom, t)
+        keyspace = M.mask_keyspace(mask, custom, t)
         if host_only:
             if increment:
                 lo, hi = increment[0], min(increment[1] or npos, npos)
@@ -117,15 +136,22 @@ def main(argv=None) -> int:
             else:
                 masks = [mask]
             if a.keyspace:
-                print(sum(M.mask_keyspace(m, custom) for m in masks))
+                print(sum(M.mask_keyspace(m, custom, t) for m in masks))
                 return 0
+            model = None if a.markov is None else M.markov_load(a.markov)
             out = sys.stdout.buffer
             for m in masks:
-                k = M.mask_keyspace(m, custom)
+                k = M.mask_keyspace(m, custom, t)
                 if a.skip >= k:
                     return _fail("--skip is not below the keyspace")
-                for i in range(a.skip, min(k, a.skip + a.limit) if a.limit else k):
-                    out.write(M.mask_candidate(m, i, custom) + b"\n")
+                end = min(k, a.skip + a.limit) if a.limit else k
+                if model is None:
+                    for i in range(a.skip, end):
+                        out.write(M.mask_candidate(m, i, custom) + b"\n")
+                else:  # the Markov order, 4096 indices per call: the model is validated once per call
+                    for i in range(a.skip, end, 4096):
+                        out.write(b"".join(c + b"\n" for c in M.mask_candidates(m, range(i, min(end, i + 4096)), custom,
+                                                                                model, t)))
             out.flush()
             return 0
         devices = _devices(a)
@@ -134,7 +160,7 @@ def main(argv=None) -> int:
         if not increment and a.skip >= keyspace:
             return _fail("--skip is not below the keyspace")
         rc = M.crack_mask(a.args[0], mask, custom, a.skip, a.limit, increment, a.nonce_error_corrections, a.outfile,
-                          device_mask=devices, batch=a.batch)
+                          device_mask=devices, batch=a.batch, markov=a.markov, threshold=t)
     except L.DwpaError as e:
         return _fail(str(e))
     if rc in (0, 1):

@@ -44,7 +44,10 @@ extern "C" {
                                 attack -- dwpa_mask_keyspace, dwpa_mask_candidate, dwpa_scan_set_mask,
                                 dwpa_scan_load_mask, dwpa_crack_mask; the hybrid attacks -- dwpa_scan_load_hybrid,
                                 dwpa_crack_hybrid; the combinator attack -- dwpa_scan_load_combinator,
-                                dwpa_crack_combinator */
+                                dwpa_crack_combinator; the mask attack in Markov order -- dwpa_markov_train,
+                                dwpa_markov_load, dwpa_markov_check, dwpa_mask_keyspace_markov,
+                                dwpa_mask_candidate_markov, dwpa_mask_candidates_markov, dwpa_scan_set_mask_markov,
+                                dwpa_crack_mask_markov */
 
 /* ---- return codes ------------------------------------------------------------------------------------------ */
 #define DWPA_MISS 0            /* no key matched (PHP: False)                                                 */
@@ -326,6 +329,51 @@ int dwpa_crack_mask(const char *hash_file, const char *mask, const dwpa_bytes cu
                     uint32_t increment_min, uint32_t increment_max, int nonce_error_corrections, const char *out_file,
                     const dwpa_config *cfg);
 
+/* ---- mask attack in Markov order with a per-position threshold: hashcat -a 3 [-t N] ---------------------------
+ * (Added without a new ABI version, discoverable by symbol.)
+ * Model: position-dependent, first order, over bytes, positions 0..62.  n[p][a][b] = the training words whose byte
+ * at position p is b and whose byte at position p - 1 is a (the predecessor of position 0 is byte 0); order[p][a] =
+ * the 256 byte values by n[p][a][b] descending, ties by byte value ascending, so an unseen byte ranks after every
+ * seen one, in byte order.  A model file (DWPA_MARKOV_BYTES bytes) holds the ranking, not the counts: the 8 bytes
+ * "DWPAMKV1", u32 LE 63, u32 LE 0, then order as 63 x 256 rows of 256 bytes.  A model image is such a file in memory;
+ * every call that takes one refuses (DWPA_E_ARG) another size, another header, or a row that is no permutation of
+ * 0..255.  There are no built-in statistics, and hashcat's own statistics file (hashcat.hcstat2) is not read.
+ * Keyspace: for the mask's sets S_p (sizes n_p) and a threshold t (0 = none, else 1..256; above: DWPA_E_ARG), r_p =
+ * n_p (t = 0) or min(n_p, t) and K = the product of the r_p, at most 2^64 - 1 (the un-thresholded mask's keyspace
+ * may be larger).  K needs no model.
+ * Order -- this library's own: the digits d_p of candidate i over the radices r_p, LAST position fastest; bytes c_0 =
+ * row(0, 0)[d_0], c_p = row(p, c_{p-1})[d_p], where row(p, a) is order[p][a] filtered to the members of S_p, its
+ * first r_p entries.  A literal is a position of radix 1: its own byte whatever the model says, and the predecessor
+ * of the next position.  Distinct indices give distinct candidates; with t = 0 the candidate set is the plain mask's,
+ * with t > 0 a subset of it.  Parity of the index with hashcat's Markov order is unpinned. */
+#define DWPA_MARKOV_BYTES 4128784
+/* Host only.  Trains a model from word lists read as every attack reads them (plain or gzip, "\n" or "\r\n", $HEX[]
+ * decoded), several lists counting as their concatenation; a word contributes its first 63 bytes, an empty line
+ * nothing.  Writes out_file and stores the number of contributing words in *words (nullable).  DWPA_E_IO: a list
+ * that cannot be read or a damaged gzip stream (counted up to the damage, no file written), out_file not writable. */
+int dwpa_markov_train(const char *const *dicts, size_t ndicts, const char *out_file, uint64_t *words);
+/* Host only.  The model file at path, validated, into out (cap >= DWPA_MARKOV_BYTES).  DWPA_E_IO: unreadable;
+ * DWPA_E_ARG: not a model file.  dwpa_markov_check validates an image in memory. */
+int dwpa_markov_load(const char *path, uint8_t *out, size_t cap);
+int dwpa_markov_check(const uint8_t *model, size_t model_len);
+/* Host only: dwpa_mask_keyspace / dwpa_mask_candidate under a threshold and a model image.
+ * dwpa_mask_candidates_markov: n indices at once (the image is validated once), out = n x 64 bytes. */
+int dwpa_mask_keyspace_markov(const char *mask, size_t mask_len, const dwpa_bytes custom[4], uint32_t threshold,
+                              uint32_t *positions, uint64_t *keyspace);
+int dwpa_mask_candidate_markov(const char *mask, size_t mask_len, const dwpa_bytes custom[4], const uint8_t *model,
+                               size_t model_len, uint32_t threshold, uint64_t index, uint8_t out[64],
+                               uint32_t *out_len);
+int dwpa_mask_candidates_markov(const char *mask, size_t mask_len, const dwpa_bytes custom[4], const uint8_t *model,
+                                size_t model_len, uint32_t threshold, const uint64_t *indices, size_t n,
+                                uint8_t *out, uint32_t *out_len);
+/* dwpa_crack_mask in Markov order: markov_file is a model file, skip / limit index the thresholded keyspace, and
+ * with increment one model serves every prefix.  A missing or damaged model file, or a threshold above 256, is
+ * DWPA_RC_ERROR before any device is touched.  In every other respect dwpa_crack_mask. */
+int dwpa_crack_mask_markov(const char *hash_file, const char *mask, const dwpa_bytes custom[4],
+                           const char *markov_file, uint32_t threshold, uint64_t skip, uint64_t limit,
+                           uint32_t increment_min, uint32_t increment_max, int nonce_error_corrections,
+                           const char *out_file, const dwpa_config *cfg);
+
 /* ---- hybrid attacks: hashcat -a 6 (wordlist || mask) and -a 7 (mask || wordlist) ------------------------------
  * Candidate: mode 6 = word || m, mode 7 = m || word, m a candidate of the mask (the mask language above, 1..63
  * positions, keyspace K).
@@ -536,6 +584,13 @@ int dwpa_scan_load_numeric(dwpa_scan *scan, uint64_t first, uint32_t count, uint
 int dwpa_scan_set_mask(dwpa_scan *scan, const char *mask, size_t mask_len, const dwpa_bytes custom[4],
                        uint64_t *keyspace);
 int dwpa_scan_load_mask(dwpa_scan *scan, uint64_t first, uint32_t count, void *hip_stream);
+/* The scan's mask in Markov order under a threshold ("mask attack in Markov order" above): uploads one table of
+ * 256 B + 64 KiB per position, *keyspace (nullable) receives the thresholded K, and dwpa_scan_load_mask then generates
+ * that order's candidates [first, first + count) (first + count <= K).  It replaces a mask set by either call, and
+ * dwpa_scan_set_mask replaces it; while it is set the scan has no mask for dwpa_scan_load_hybrid.  DWPA_E_ARG (the
+ * mask set before stays): an invalid mask, threshold above 256, K above 2^64 - 1, not a model image. */
+int dwpa_scan_set_mask_markov(dwpa_scan *scan, const char *mask, size_t mask_len, const dwpa_bytes custom[4],
+                              const uint8_t *model, size_t model_len, uint32_t threshold, uint64_t *keyspace);
 /* Hybrid candidates ("hybrid attacks" above) of words [first_word, first_word + nwords) of an HBM-resident dictionary
  * (d_offsets: at least first_word + nwords + 1 offsets) x the indices [mask_first, mask_first + mask_count) of the
  * mask set by dwpa_scan_set_mask, word-major: nwords * mask_count raw candidates, the kept ones compacted into slots
