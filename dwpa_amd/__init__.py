@@ -19,6 +19,10 @@ this package is its Python host side:
   (``python -m dwpa_amd.chain``); :meth:`Scan.set_chain` / :meth:`Scan.load_chain` are its scan-path calls,
   :func:`chain_keyspace` / :func:`chain_split` / :func:`chain_candidate` its host-only helpers; a list part may
   carry hashcat rules (``crack_chain(..., rules=)``, :meth:`Scan.set_chain_rules`, ``chain_candidate(..., rules=)``)
+* :func:`crack_table`      -- table attack (hashcat-legacy ``-a 5 --table-file``, toggle-case ``-a 2``): every
+  combination of per-byte alternatives of every word (``python -m dwpa_amd.table``); :meth:`Scan.set_table` /
+  :meth:`Scan.load_table` are its scan-path calls, :func:`table_parse` / :func:`table_builtin` /
+  :func:`table_keyspace` / :func:`table_candidates` its host-only helpers
 * :mod:`dwpa_amd.help_crack` -- ``run_cracker`` replacement for help_crack.py
 """
 from ._lib import (DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS, DWPA_COMBI_AMP_LEFT,  # noqa: F401
@@ -26,7 +30,8 @@ from ._lib import (DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS, DWPA_
 from .m22000 import (BatchJobs, chain_candidate, chain_keyspace, chain_split, check_batch,  # noqa: F401
                      check_key_m22000, crack_chain, crack_combinator, crack_files, crack_hybrid, crack_mask,
                      device_count, group_by_essid, markov_load, markov_train, mask_candidate, mask_candidates, mask_keyspace, check_stats, hash_m22000, hc_unhex, init,
-                     parse_m22000, pbkdf2_pmk, rules_count, rules_count_ex, rules_expand, Scan)
+                     parse_m22000, pbkdf2_pmk, rules_count, rules_count_ex, rules_expand, Scan, crack_table, table_builtin,
+                     table_candidates, table_keyspace, table_parse)
 
 __all__ = ["DwpaError", "load", "BatchJobs", "check_key_m22000", "check_batch", "pbkdf2_pmk", "hc_unhex", "hash_m22000",
            "crack_files", "rules_count", "rules_count_ex", "check_stats", "rules_expand", "device_count", "Scan",
@@ -34,4 +39,4 @@ __all__ = ["DwpaError", "load", "BatchJobs", "check_key_m22000", "check_batch", 
            "crack_hybrid", "DWPA_HYBRID_WORD_MASK", "DWPA_HYBRID_MASK_WORD",
            "crack_combinator", "DWPA_COMBI_AMP_RIGHT", "DWPA_COMBI_AMP_LEFT",
            "crack_chain", "chain_keyspace", "chain_split", "chain_candidate", "DWPA_CHAIN_LIST", "DWPA_CHAIN_MASK",
-           "DWPA_CHAIN_MAX_PARTS"]
+           "DWPA_CHAIN_MAX_PARTS", "crack_table", "table_parse", "table_builtin", "table_keyspace", "table_candidates"]

@@ -24,6 +24,7 @@ DWPA_HYBRID_WORD_MASK, DWPA_HYBRID_MASK_WORD = 6, 7  # hashcat -a 6 (word || mas
 DWPA_COMBI_AMP_RIGHT, DWPA_COMBI_AMP_LEFT = 0, 1  # hashcat -a 1: the list held whole in device memory
 DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS = 0, 1, 4  # chain attack: the kind of a part, the most parts
 DWPA_MARKOV_BYTES = 4128784  # a Markov model file / image: 16-byte header + 63 x 256 rows of 256 bytes
+DWPA_TABLE_MAX_ALT, DWPA_TABLE_IMAGE_BYTES = 16, 4352  # table attack: alternatives per byte, the parsed table image
 DWPA_DICT_OK, DWPA_DICT_DAMAGED = 0, 1  # dwpa_crack_files_ex per-dictionary status (or DWPA_E_IO)
 DWPA_RULES_DEFAULT, DWPA_RULES_HASHCAT, DWPA_RULES_FULL = 0, 1, 2  # dwpa_config.rule_mode
 DWPA_BACKEND_DEVICE, DWPA_BACKEND_HOST_SMALL, DWPA_BACKEND_HOST_FALLBACK = 0, 1, 2  # dwpa_check_stats.backend
@@ -202,6 +203,19 @@ SIGNATURES = {
     "dwpa_crack_mask_markov": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(Bytes), ctypes.c_char_p,
                                 ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
                                 ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)], ctypes.c_int),
+    "dwpa_table_parse": ([ctypes.c_char_p, ctypes.c_size_t, _P, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+    "dwpa_table_builtin": ([ctypes.c_char_p, _P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dwpa_table_keyspace": ([ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(Bytes), ctypes.c_size_t, ctypes.c_uint32,
+                             ctypes.c_uint32, ctypes.c_uint32] + [ctypes.POINTER(ctypes.c_uint64)] * 4, ctypes.c_int),
+    "dwpa_table_candidates": ([ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(Bytes), ctypes.c_size_t,
+                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
+                               ctypes.c_size_t, _P, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+    "dwpa_scan_set_table": ([_P, _P, _P, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32,
+                             ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64),
+                             ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_scan_load_table": ([_P, ctypes.c_uint64, ctypes.c_uint32, _P], ctypes.c_int),
+    "dwpa_crack_table": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64,
+                          ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)], ctypes.c_int),
     "dwpa_scan_pbkdf2": ([_P, ctypes.c_int, _P], ctypes.c_int),
     "dwpa_scan_verify": ([_P, ctypes.c_int, _P], ctypes.c_int),
     "dwpa_scan_run": ([_P, _P], ctypes.c_int),

@@ -10,6 +10,9 @@
 //   dwpa_crack_chain_rules(): the same with a rules file on any list part (chain_rules_dev.hip): that part's choices
 //                       are its (rule, word) pairs, rule-major, and a hit's PSK takes the rule through
 //                       RuleSet::apply_host.
+//   dwpa_crack_table(): one word list under a substitution table (table.hpp): every combination of the per-byte
+//                       alternatives of every kept word.  The keyspace is a prefix sum over the words; one segment
+//                       of raw indices [skip, skip + limit).
 //
 // There is no dictionary feed, so none of crack.cpp's reader / item-queue machinery: every worker --
 // DWPA_CRACK_SHARDS_PER_DEVICE per selected device -- takes batch-sized ascending index ranges from one shared cursor
@@ -42,6 +45,7 @@
 #include "markov.hpp"
 #include "mask.hpp"
 #include "rules.hpp"
+#include "table.hpp"
 
 namespace dwpa {
 
@@ -470,9 +474,125 @@ int crack_chain_impl(const char* hash_file, const dwpa_chain_spec* specs, uint32
     return crack_range(call, hash_file, nec, out_file, cfg, std::move(segs), attack);
 }
 
+// The table attack (table.hpp): one list held whole, the table, and the kept-word index built on the host, which names
+// the keyspace before any device is touched and rebuilds a hit's PSK.  Every worker's scan builds its own index on its
+// device (scan_set_table); the two must agree.
+struct TableAttack {
+    Table table;
+    TableFilter filter;
+    HostList list;
+    TableIndex index;
+
+    struct Worker {
+        const TableAttack& at;
+        int device = 0;
+        DevBuf off, bytes;  // the list on this worker's device
+        explicit Worker(const TableAttack& a) : at(a) {}
+        ~Worker() {
+            (void)hipSetDevice(device);
+            off.release();
+            bytes.release();
+        }
+        int open(ScanWorker& w) {
+            device = w.device;
+            int r = upload_list(at.list, &off, &bytes);
+            if (r < 0) return r;
+            uint64_t K = 0, kept = 0;
+            r = scan_set_table(w.scan, (const uint64_t*)off.p, (const uint8_t*)bytes.p, at.list.words(), at.table,
+                               at.filter.minlen, at.filter.maxlen, at.filter.word_max, &K, &kept);
+            if (r < 0) return r;
+            return K == at.index.keyspace() && kept == at.index.kept() ? 0 : DWPA_E_HIP;
+        }
+        int enter(ScanWorker&, size_t) { return 0; }
+        int load(ScanWorker& w, uint64_t first, uint32_t count) { return scan_load_table(w.scan, first, count, w.stream); }
+        int counted(ScanWorker&, uint32_t count, uint64_t* n) {
+            *n = count;  // every index is a candidate: nothing to read back
+            return 0;
+        }
+        bool plain_of(uint64_t id, std::string* psk) const {
+            uint8_t m[64];
+            uint32_t len;
+            if (!table_candidate(at.table, at.index, at.list.off.data(), (const uint8_t*)at.list.bytes.data(), id, m,
+                                 &len))
+                return false;
+            psk->assign((const char*)m, len);
+            return true;
+        }
+    };
+};
+
+int crack_table_impl(const char* hash_file, const char* dict, const char* table_file, uint32_t word_max, uint64_t skip,
+                     uint64_t limit, int nec, const char* out_file, const dwpa_config* cfg) {
+    CrackCall call;
+    if (!hash_file || !dict || !table_file || !out_file) return DWPA_RC_ERROR;
+    if (!crack_check_args(cfg, nec)) return DWPA_RC_ERROR;
+    auto attack = std::make_unique<TableAttack>();
+    attack->filter = table_filter(8, TABLE_MAX_LEN, word_max);
+    uint32_t bad_line = 0;
+    const int tr = table_read_file(table_file, &attack->table, &bad_line);
+    if (tr == DWPA_E_IO) {
+        fprintf(stderr, "[dwpa] table %s: cannot be read\n", table_file);
+        return DWPA_RC_ERROR;
+    }
+    if (tr < 0) {
+        fprintf(stderr, "[dwpa] table %s: line %u is not K=V (one byte or \\xHH each), is a 17th alternative for its "
+                        "key, or the file holds no mapping\n", table_file, bad_line);
+        return DWPA_RC_ERROR;
+    }
+    {
+        FILE* f = fopen(hash_file, "rb");
+        if (!f) {
+            fprintf(stderr, "[dwpa] hash file %s: cannot be opened\n", hash_file);
+            return DWPA_RC_ERROR;
+        }
+        fclose(f);
+    }
+    const int lr = read_list(dict, &attack->list);
+    if (lr == DWPA_E_OVERFLOW) {
+        fprintf(stderr, "[dwpa] list %s: too large to hold (at most %llu bytes of text and offsets, fewer than 2^32 "
+                        "words)\n", dict, (unsigned long long)DWPA_COMBI_AMP_MAX_BYTES);
+        return DWPA_RC_ERROR;
+    }
+    if (lr < 0) {
+        fprintf(stderr, "[dwpa] list %s: cannot be read\n", dict);
+        return DWPA_RC_ERROR;
+    }
+    const HostList& l = attack->list;
+    call.st.words = l.words();
+    if (table_index_list(attack->table, attack->filter, l.off.data(), (const uint8_t*)l.bytes.data(), (size_t)l.words(),
+                         &attack->index) < 0) {
+        fprintf(stderr, "[dwpa] the table attack's keyspace is above 2^64 - 1\n");
+        return DWPA_RC_ERROR;
+    }
+    const TableIndex& ix = attack->index;
+    fprintf(stderr, "[dwpa] table attack: %llu of %llu words kept, %llu dropped for length, %llu for more than %u "
+                    "candidates\n", (unsigned long long)ix.kept(), (unsigned long long)l.words(),
+            (unsigned long long)ix.dropped_len, (unsigned long long)ix.dropped_max, attack->filter.word_max);
+    const uint64_t K = ix.keyspace();
+    if (K > 0 && skip >= K) {
+        fprintf(stderr, "[dwpa] --skip is not below the keyspace\n");
+        return DWPA_RC_ERROR;
+    }
+    std::vector<RangeSegment> segs;  // K = 0 (no word kept): nothing to run, the call exhausts
+    if (K > 0) {
+        const uint64_t room = K - skip;
+        segs.push_back(RangeSegment{skip, skip + (limit && limit < room ? limit : room)});
+    }
+    return crack_range(call, hash_file, nec, out_file, cfg, std::move(segs), *attack);
+}
+
 }  // namespace
 
 }  // namespace dwpa
+
+extern "C" int dwpa_crack_table(const char* hash_file, const char* dict, const char* table_file, uint32_t word_max,
+                                uint64_t skip, uint64_t limit, int nonce_error_corrections, const char* out_file,
+                                const dwpa_config* cfg) {
+    return dwpa::guarded([&]() -> int {
+        return dwpa::crack_table_impl(hash_file, dict, table_file, word_max, skip, limit, nonce_error_corrections,
+                                      out_file, cfg);
+    }, DWPA_RC_ERROR, DWPA_RC_ERROR);
+}
 
 extern "C" int dwpa_crack_mask(const char* hash_file, const char* mask, const dwpa_bytes custom[4], uint64_t skip,
                                uint64_t limit, uint32_t increment_min, uint32_t increment_max,

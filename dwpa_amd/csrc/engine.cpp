@@ -34,6 +34,7 @@
 #include "kernels.hpp"
 #include "m22000_host.hpp"
 #include "markov.hpp"
+#include "table.hpp"
 #include "mask.hpp"
 #include "chain.hpp"
 #include "rules.hpp"
@@ -1508,6 +1509,14 @@ struct dwpa_scan {
     uint32_t chain_nparts = 0;
     uint64_t chain_keyspace = 0;
     ChainPart chain[DWPA_CHAIN_MAX_PARTS];
+    // dwpa_scan_set_table: the caller's list (device pointers, as a chain list), and what the scan owns: the table
+    // image and the kept-word index (table.hpp TableIndex) on the device.  Independent of the mask and the chain.
+    bool table_set = false;
+    const uint64_t* table_off = nullptr;
+    const uint8_t* table_bytes = nullptr;
+    uint64_t table_keyspace = 0;
+    uint32_t table_nkept = 0;
+    dwpa::DevBuf table_tab, table_start, table_kword;
 };
 
 namespace dwpa {
@@ -1578,6 +1587,7 @@ void scan_destroy(dwpa_scan* sc) {
     sc->mg_pmk.release(); sc->mg_gsalt.release(); sc->mg_list.release(); sc->mg_poff.release();
     sc->mask_tab.release();
     sc->markov_tab.release();
+    sc->table_tab.release(); sc->table_start.release(); sc->table_kword.release();
     for (auto& cp : sc->chain) {
         cp.tab.release();
         rules_release(&cp.rules);
@@ -1676,6 +1686,61 @@ int scan_load_mask(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream) 
     HIPCHK(launch_prep_mask(digits, first, count, sc->mask.npos, (const uint8_t*)sc->mask_tab.p,
                             (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p, (uint32_t*)sc->batch.counters.p,
                             sc->batch_cap, as_stream(stream)));
+    return 0;
+}
+
+// The table attack (table_dev.hip).  The counts come from the device, the index from the host: the count kernel runs
+// over the caller's list into buffers of this call's own, and only when K is known to fit does the scan change -- so a
+// refused call leaves the previous table in force.  The launches that still read the old index are waited for first.
+int scan_set_table(dwpa_scan* sc, const uint64_t* d_off, const uint8_t* d_bytes, uint64_t nwords, const Table& t,
+                   uint32_t minlen, uint32_t maxlen, uint32_t word_max, uint64_t* keyspace, uint64_t* kept) {
+    if (!sc || nwords > UINT32_MAX || (nwords && (!d_off || !d_bytes))) return DWPA_E_ARG;
+    const TableFilter f = table_filter(minlen, maxlen, word_max);
+    HIPCHK(hipSetDevice(sc->device));
+    DevBuf tab, counts, start, kword;
+    auto drop = [&](int r) {
+        tab.release(); counts.release(); start.release(); kword.release();
+        return r;
+    };
+    int r;
+    if ((r = tab.ensure(sizeof(Table))) < 0 || (r = counts.ensure((size_t)nwords * 4)) < 0) return drop(r);
+    std::vector<uint32_t> hc((size_t)nwords);
+    if (hipMemcpy(tab.p, &t, sizeof(Table), hipMemcpyHostToDevice) != hipSuccess ||
+        launch_table_count(d_off, d_bytes, (uint32_t)nwords, (const uint8_t*)tab.p, f.minlen, f.maxlen, f.word_max,
+                           (uint32_t*)counts.p, nullptr) != hipSuccess ||
+        (nwords && hipMemcpy(hc.data(), counts.p, (size_t)nwords * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        return drop(DWPA_E_HIP);
+    counts.release();
+    TableIndex ix;
+    if ((r = table_index_counts(hc.data(), (size_t)nwords, &ix)) < 0) return drop(r);  // K above 2^64 - 1
+    if ((r = start.ensure(ix.start.size() * 8)) < 0 || (r = kword.ensure(ix.kword.size() * 4)) < 0) return drop(r);
+    if (hipMemcpy(start.p, ix.start.data(), ix.start.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        (ix.kept() && hipMemcpy(kword.p, ix.kword.data(), ix.kword.size() * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+        hipDeviceSynchronize() != hipSuccess)
+        return drop(DWPA_E_HIP);
+    std::swap(sc->table_tab, tab);
+    std::swap(sc->table_start, start);
+    std::swap(sc->table_kword, kword);
+    sc->table_off = d_off;
+    sc->table_bytes = d_bytes;
+    sc->table_keyspace = ix.keyspace();
+    sc->table_nkept = (uint32_t)ix.kept();
+    sc->table_set = true;
+    if (keyspace) *keyspace = ix.keyspace();
+    if (kept) *kept = ix.kept();
+    return drop(0);  // the previous table's buffers
+}
+
+// No host synchronisation: the kernel finds each index's word itself and writes the loaded count.
+int scan_load_table(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream) {
+    if (!sc || !sc->table_set || count > sc->batch_cap) return DWPA_E_ARG;
+    const uint64_t K = sc->table_keyspace;
+    if (first > K || count > K - first) return DWPA_E_ARG;  // first + count > K, also when the sum wraps
+    HIPCHK(hipSetDevice(sc->device));
+    HIPCHK(launch_prep_table(first, count, sc->table_nkept, (const uint64_t*)sc->table_start.p,
+                             (const uint32_t*)sc->table_kword.p, sc->table_off, sc->table_bytes,
+                             (const uint8_t*)sc->table_tab.p, (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
+                             (uint32_t*)sc->batch.counters.p, sc->batch_cap, as_stream(stream)));
     return 0;
 }
 
@@ -2364,6 +2429,27 @@ int dwpa_scan_load_chain(dwpa_scan* scan, uint64_t first, uint32_t count, uint32
     return guarded([&]() -> int {
         if (!scan) RCHK(ensure_init());
         return scan_load_chain(scan, first, count, minlen, maxlen, hip_stream);
+    });
+}
+int dwpa_scan_set_table(dwpa_scan* scan, const uint64_t* d_offsets, const uint8_t* d_bytes, uint64_t nwords,
+                        const char* table_text, size_t table_len, uint32_t minlen, uint32_t maxlen, uint32_t word_max,
+                        uint64_t* keyspace, uint64_t* kept) {
+    return guarded([&]() -> int {
+        if (!scan) {  // no scan can exist without a device: say so first
+            RCHK(ensure_init());
+            return DWPA_E_ARG;
+        }
+        // the call and the table are checked before anything on the device is touched
+        if (nwords > UINT32_MAX || (nwords && (!d_offsets || !d_bytes))) return DWPA_E_ARG;
+        Table t;
+        RCHK(table_parse(table_text, table_len, &t, nullptr));
+        return scan_set_table(scan, d_offsets, d_bytes, nwords, t, minlen, maxlen, word_max, keyspace, kept);
+    });
+}
+int dwpa_scan_load_table(dwpa_scan* scan, uint64_t first, uint32_t count, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!scan) RCHK(ensure_init());
+        return scan_load_table(scan, first, count, hip_stream);
     });
 }
 int dwpa_scan_pbkdf2(dwpa_scan* scan, int group, void* hip_stream) {

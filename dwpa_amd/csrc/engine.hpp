@@ -121,6 +121,12 @@ int scan_set_chain(dwpa_scan* sc, const dwpa_chain_part* parts, uint32_t nparts,
 struct RuleSet;  // rules.hpp
 int scan_set_chain_rules(dwpa_scan* sc, uint32_t part, const RuleSet* rs, uint64_t* keyspace);
 int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen, void* stream);
+// the table attack (table_dev.hip): the list's device pointers stay the caller's, the scan owns the table image and
+// the kept-word index it builds from the count kernel's output.  A refused call leaves the previous table set.
+struct Table;  // table.hpp
+int scan_set_table(dwpa_scan* sc, const uint64_t* d_off, const uint8_t* d_bytes, uint64_t nwords, const Table& t,
+                   uint32_t minlen, uint32_t maxlen, uint32_t word_max, uint64_t* keyspace, uint64_t* kept);
+int scan_load_table(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream);
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream);
 int scan_verify(dwpa_scan* sc, int group, void* stream);
 int scan_run(dwpa_scan* sc, void* stream);

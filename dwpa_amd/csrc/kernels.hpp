@@ -28,6 +28,16 @@ hipError_t launch_prep_mask(const uint8_t digits[64], uint64_t first, uint32_t c
 hipError_t launch_prep_markov(const uint8_t digits[64], uint64_t first, uint32_t count, uint32_t npos,
                               const uint8_t* table, uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap,
                               hipStream_t s);
+// table_dev.hip: counts[i] = word i's candidate count under the table image (table.hpp Table), 0 for a word the filter
+// drops (length outside minlen..min(maxlen, 63), count above word_max >= 1).  off: nwords + 1 byte offsets.
+hipError_t launch_table_count(const uint64_t* off, const uint8_t* bytes, uint32_t nwords, const uint8_t* table,
+                              uint32_t minlen, uint32_t maxlen, uint32_t word_max, uint32_t* counts, hipStream_t s);
+// table candidates [first, first + count) -> midstates, ids[slot] = first + slot, *counter = count (written by the
+// kernel).  start: nkept + 1 prefix sums of the kept words' counts, kword: their nkept list indices (table.hpp
+// TableIndex), both on the device.  The caller has checked first + count <= start[nkept] and count <= cap.
+hipError_t launch_prep_table(uint64_t first, uint32_t count, uint32_t nkept, const uint64_t* start,
+                             const uint32_t* kword, const uint64_t* off, const uint8_t* bytes, const uint8_t* table,
+                             uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap, hipStream_t s);
 // hybrid_dev.hip: words [first_word, first_word + nwords) of off/bytes x mask candidates [mask_first, mask_first +
 // mask_count), word-major, joined as word || mask or (mask_then_word) mask || word -> midstates in compacted slots;
 // kept iff len <= 63 and minlen <= len + npos <= min(maxlen, 64); ids[slot] = word * keyspace + mask index.  The

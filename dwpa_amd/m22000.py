@@ -532,6 +532,92 @@ def crack_chain(hash_file, parts, custom=(), skip: int = 0, limit: int = 0, nonc
     return rc, [int(st[i]) for i in range(len(specs))]
 
 
+def _word_array(words):
+    """A sequence of words -> (ctypes array of Bytes, keep-alive): one buffer for all of them."""
+    ws = [_b(w) for w in words]
+    buf = ctypes.create_string_buffer(b"".join(ws), sum(len(w) for w in ws) + 1)
+    base = ctypes.addressof(buf)
+    arr = (L.Bytes * max(1, len(ws)))()
+    pos = 0
+    for i, w in enumerate(ws):
+        arr[i].ptr, arr[i].len = base + pos, len(w)
+        pos += len(w)
+    return arr, len(ws), buf
+
+
+def _u32(v, what) -> int:
+    v = int(v)
+    if not 0 <= v < 2**32:
+        raise L.DwpaError(L.DWPA_E_ARG, f"{what} {v} is outside uint32")
+    return v
+
+
+def table_builtin(name="toggle") -> bytes:
+    """The text of a built-in substitution table: "toggle" maps every ASCII letter to [itself, the other case]."""
+    n = ctypes.c_size_t(0)
+    L.check(L.load().dwpa_table_builtin(_b(name), None, 0, ctypes.byref(n)), "table_builtin")
+    out = ctypes.create_string_buffer(n.value + 1)
+    L.check(L.load().dwpa_table_builtin(_b(name), out, n.value, ctypes.byref(n)), "table_builtin")
+    return out.raw[:n.value]
+
+
+def table_parse(table) -> dict:
+    """A table text (include/dwpa22000.h "table attack": K=V lines, each side one byte or \\xHH) as {byte: bytes of
+    its alternatives in file order} for all 256 byte values (host only).  Raises DwpaError(DWPA_E_ARG) naming the
+    line at fault (.line) for a line that is not K=V, a 17th alternative for one key, or a text with no mapping."""
+    t = _b(table)
+    img = ctypes.create_string_buffer(L.DWPA_TABLE_IMAGE_BYTES)
+    bad = ctypes.c_uint32(0)
+    rc = L.load().dwpa_table_parse(t, len(t), img, ctypes.byref(bad))
+    if rc < 0:
+        e = L.DwpaError(rc, f"table: line {bad.value} is not K=V, is a 17th alternative for its key, or the text holds "
+                            "no mapping")
+        e.line = bad.value
+        raise e
+    raw = img.raw
+    return {c: raw[256 + 16 * c:256 + 16 * c + raw[c]] for c in range(256)}
+
+
+def table_keyspace(table, words, minlen: int = 8, maxlen: int = 63, word_max: int = 0) -> dict:
+    """The table attack's keyspace over a word list (host only): {keyspace, kept, dropped_len, dropped_max}.  A word is
+    kept iff its length is in minlen..min(maxlen, 63) and the product of its bytes' alternative counts is at most
+    word_max (0: 2**32 - 1).  Raises DwpaError(DWPA_E_ARG) for an invalid table or a keyspace above 2**64 - 1."""
+    t = _b(table)
+    arr, n, keep = _word_array(words)
+    v = [ctypes.c_uint64(0) for _ in range(4)]
+    L.check(L.load().dwpa_table_keyspace(t, len(t), arr, n, _u32(minlen, "minlen"), _u32(maxlen, "maxlen"),
+                                         _u32(word_max, "word_max"), *[ctypes.byref(x) for x in v]), "table_keyspace")
+    return dict(zip(("keyspace", "kept", "dropped_len", "dropped_max"), (x.value for x in v)))
+
+
+def table_candidates(table, words, indices, minlen: int = 8, maxlen: int = 63, word_max: int = 0) -> list:
+    """Candidates `indices` of the table attack over a word list (host only), in the library's order: kept words in
+    list order, within a word itertools.product over its bytes' alternative lists (the last position fastest)."""
+    t = _b(table)
+    arr, n, keep = _word_array(words)
+    idx = [_u64(i, "index") for i in indices]
+    ia = (ctypes.c_uint64 * max(1, len(idx)))(*idx)
+    out = ctypes.create_string_buffer(64 * max(1, len(idx)))
+    ol = (ctypes.c_uint32 * max(1, len(idx)))()
+    L.check(L.load().dwpa_table_candidates(t, len(t), arr, n, _u32(minlen, "minlen"), _u32(maxlen, "maxlen"),
+                                           _u32(word_max, "word_max"), ia, len(idx), out, ol), "table_candidates")
+    raw = out.raw
+    return [raw[64 * k:64 * k + ol[k]] for k in range(len(idx))]
+
+
+def crack_table(hash_file, dict_file, table_file, word_max: int = 0, skip: int = 0, limit: int = 0,
+                nonce_error_corrections: int = 8, out_file="help_crack.key", device_mask: int = 0, batch: int = 0,
+                nc_mode: int = L.DWPA_NC_HASHCAT) -> int:
+    """The table attack over hash_file, on every selected device: every combination of the per-byte alternatives of
+    table_file (K=V lines) for every word of dict_file (plain or gzip) of 8..63 bytes with at most word_max
+    combinations (0: 2**32 - 1).  skip / limit: indices [skip, skip + limit) of the keyspace (limit 0 = to the end).
+    Returns a hashcat exit code (0 cracked, 1 exhausted, -1 error)."""
+    cfg = L.Config(ctypes.sizeof(L.Config), device_mask, batch, nc_mode)
+    return L.load().dwpa_crack_table(_b(hash_file), _b(dict_file), _b(table_file), _u32(word_max, "word_max"),
+                                     _u64(skip, "skip"), _u64(limit, "limit"), _nc(nonce_error_corrections),
+                                     _b(out_file), ctypes.byref(cfg))
+
+
 def crack_stats():
     """dwpa_crack_last_stats: {words, candidates, hashes, cracked, seconds, rules, rules_skipped, rules_rejmem} of
     this thread's last crack call."""
@@ -687,6 +773,25 @@ class Scan:
                 raise L.DwpaError(L.DWPA_E_ARG, f"{what} {v} is outside uint32")
         L.check(self._lib.dwpa_scan_load_chain(self._h, _u64(first, "first"), int(count), int(minlen), int(maxlen),
                                                stream), "scan_load_chain")
+
+    def set_table(self, d_offsets: int, d_bytes: int, nwords: int, table, minlen: int = 8, maxlen: int = 63,
+                  word_max: int = 0):
+        """Set the scan's table attack: an HBM-resident list (nwords + 1 byte offsets and the bytes, which the caller
+        keeps alive) under a table text.  The words are counted on the GPU and the kept-word index is built and kept
+        by the scan.  Returns (keyspace, kept).  The scan's mask and chain stay as they are."""
+        t = _b(table)
+        k, kept = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        L.check(self._lib.dwpa_scan_set_table(self._h, d_offsets, d_bytes, _u64(nwords, "nwords"), t, len(t),
+                                              _u32(minlen, "minlen"), _u32(maxlen, "maxlen"),
+                                              _u32(word_max, "word_max"), ctypes.byref(k), ctypes.byref(kept)),
+                "scan_set_table")
+        self.table_keyspace = k.value
+        return k.value, kept.value
+
+    def load_table(self, first: int, count: int, stream: int = 0):
+        """Table candidates [first, first + count) into slots 0..count-1, generated on the GPU; candidate id = index."""
+        L.check(self._lib.dwpa_scan_load_table(self._h, _u64(first, "first"), _u32(count, "count"), stream),
+                "scan_load_table")
 
     def pbkdf2(self, group: int = 0, stream: int = 0):
         L.check(self._lib.dwpa_scan_pbkdf2(self._h, group, stream), "scan_pbkdf2")

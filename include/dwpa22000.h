@@ -47,7 +47,9 @@ extern "C" {
                                 dwpa_crack_combinator; the mask attack in Markov order -- dwpa_markov_train,
                                 dwpa_markov_load, dwpa_markov_check, dwpa_mask_keyspace_markov,
                                 dwpa_mask_candidate_markov, dwpa_mask_candidates_markov, dwpa_scan_set_mask_markov,
-                                dwpa_crack_mask_markov */
+                                dwpa_crack_mask_markov; the table attack -- dwpa_table_parse, dwpa_table_builtin,
+                                dwpa_table_keyspace, dwpa_table_candidates, dwpa_scan_set_table,
+                                dwpa_scan_load_table, dwpa_crack_table */
 
 /* ---- return codes ------------------------------------------------------------------------------------------ */
 #define DWPA_MISS 0            /* no key matched (PHP: False)                                                 */
@@ -374,6 +376,52 @@ int dwpa_crack_mask_markov(const char *hash_file, const char *mask, const dwpa_b
                            uint32_t increment_min, uint32_t increment_max, int nonce_error_corrections,
                            const char *out_file, const dwpa_config *cfg);
 
+/* ---- table attack: per-byte substitution tables, every combination (hashcat-legacy -a 5 --table-file) ----------
+ * (Added without a new ABI version, discoverable by symbol.)
+ * Table: for every byte value c a list alt[c] of 1..DWPA_TABLE_MAX_ALT distinct replacement bytes, in the order of the
+ * text.  A byte the text never names as a key has alt[c] = [c]; a key keeps its original only if the text says so
+ * ("a=a"), as in hashcat-legacy.  Text, strict: every non-empty line, after one trailing CR is removed, is K=V, K and
+ * V each one literal byte or \xHH (so "===" maps '=' to '=' and "#=#" is a mapping, not a comment); a repeated (K, V)
+ * line is ignored; any other line, a 17th alternative for one key, or a text without any mapping is DWPA_E_ARG.
+ * Replacements are one byte each (multi-byte replacements are not supported), so a candidate has its word's length.
+ * Filter: a word of L bytes is kept iff minlen <= L <= maxlen (maxlen is clamped to 63) and its count k_w = the
+ * product of the alternative counts of its bytes is at most word_max (1..2^32 - 1; 0 means 2^32 - 1).  The product
+ * saturates: a word of 2^64 combinations is dropped, never counted as 0 or 1.  Dropped words own no indices.
+ * Order -- this library's own: kept words in list order, start[j] = the sum of the counts of the kept words before
+ * word j, K = start[nkept] <= 2^64 - 1 (above: DWPA_E_ARG).  Candidate id belongs to the kept word j with start[j] <=
+ * id < start[j + 1]; id - start[j] is the mixed-radix numeral over the word's positions, LAST position fastest
+ * (itertools.product over the positions' alternative lists).  Parity of the index with hashcat-legacy is unpinned. */
+#define DWPA_TABLE_MAX_ALT 16
+#define DWPA_TABLE_IMAGE_BYTES 4352 /* u8 nalt[256], then u8 alt[256][16] */
+/* Host only.  Parses a table text; image (nullable, DWPA_TABLE_IMAGE_BYTES) receives the table.  Returns the number of
+ * mappings kept (>= 1), or DWPA_E_ARG with *bad_line (nullable) = the 1-based number of the line at fault (a text
+ * without any mapping: its number of lines + 1). */
+int dwpa_table_parse(const char *text, size_t len, uint8_t *image, uint32_t *bad_line);
+/* Host only.  The text of a built-in table: "toggle" maps every ASCII letter to [itself, the other case] (hashcat
+ * -a 2).  *len = its length; copied into out when cap suffices (out nullable: ask for the length).  DWPA_E_ARG: no
+ * such table. */
+int dwpa_table_builtin(const char *name, char *out, size_t cap, size_t *len);
+/* Host only.  K, the number of kept words and the words dropped for their length and for word_max (all nullable) of
+ * the list words[0..nwords) under the table text.  DWPA_E_ARG: an invalid table, nwords >= 2^32, K above 2^64 - 1. */
+int dwpa_table_keyspace(const char *table_text, size_t table_len, const dwpa_bytes *words, size_t nwords,
+                        uint32_t minlen, uint32_t maxlen, uint32_t word_max, uint64_t *keyspace, uint64_t *kept,
+                        uint64_t *dropped_len, uint64_t *dropped_max);
+/* Host only.  Candidates indices[0..n) in one call: out = n x 64 bytes (candidate k at out + 64 k, zero beyond its
+ * length), out_len = n lengths.  DWPA_E_ARG also for an index >= K. */
+int dwpa_table_candidates(const char *table_text, size_t table_len, const dwpa_bytes *words, size_t nwords,
+                          uint32_t minlen, uint32_t maxlen, uint32_t word_max, const uint64_t *indices, size_t n,
+                          uint8_t *out, uint32_t *out_len);
+/* The table attack over hash_file, on every selected device: dwpa_crack_chain's hash file, outfile records, return
+ * codes (DWPA_RC_*), nonce_error_corrections and cfg handling.  dict is one plain or gzip word list ($HEX[] words
+ * decoded), read whole and held in device memory with the chain lists' limits; table_file holds the table text; the
+ * filter is 8..63 bytes and word_max; skip / limit name the indices [skip, skip + limit) (limit 0 = to the end).  A
+ * hit's PSK is rebuilt on the host from its index.  One stderr line states the words dropped for length and for
+ * word_max.  DWPA_RC_ERROR before any device is touched, one stderr line each: an unreadable or invalid table, an
+ * unreadable or oversized list, K above 2^64 - 1, skip >= K with K > 0, a missing hash file.  K = 0 exhausts. */
+int dwpa_crack_table(const char *hash_file, const char *dict, const char *table_file, uint32_t word_max,
+                     uint64_t skip, uint64_t limit, int nonce_error_corrections, const char *out_file,
+                     const dwpa_config *cfg);
+
 /* ---- hybrid attacks: hashcat -a 6 (wordlist || mask) and -a 7 (mask || wordlist) ------------------------------
  * Candidate: mode 6 = word || m, mode 7 = m || word, m a candidate of the mask (the mask language above, 1..63
  * positions, keyspace K).
@@ -648,6 +696,21 @@ int dwpa_scan_load_chain(dwpa_scan *scan, uint64_t first, uint32_t count, uint32
  * the rules of every part. */
 int dwpa_scan_set_chain_rules(dwpa_scan *scan, uint32_t part, const char *rules_text, size_t rules_len,
                               uint64_t *keyspace /* nullable */);
+/* Table candidates ("table attack" above) of an HBM-resident list (d_offsets: nwords + 1 byte offsets into d_bytes),
+ * which stays the caller's and must stay alive while the table is set.  dwpa_scan_set_table counts every word on the
+ * GPU, builds the kept-word index and keeps it with the table image (the scan owns and frees both); *keyspace and
+ * *kept (nullable) receive K and the number of kept words.  It leaves the scan's mask and chain alone, and they leave
+ * it alone.  Setting a table again replaces the previous one.  Every check on the call and on the table text comes
+ * before anything on the device is touched.  DWPA_E_ARG (the scan stays usable and keeps its previous table): an
+ * invalid table, nwords >= 2^32, a null list with nwords > 0, K above 2^64 - 1.
+ * dwpa_scan_load_table loads candidates [first, first + count): slot s holds index first + s (no compaction), the
+ * candidate id is its index and dwpa_scan_loaded then equals count.  A load does not synchronise with the host.
+ * DWPA_E_ARG: count > batch, first + count > K (also when the sum wraps), no table set.  Without a device:
+ * DWPA_E_NODEV. */
+int dwpa_scan_set_table(dwpa_scan *scan, const uint64_t *d_offsets, const uint8_t *d_bytes, uint64_t nwords,
+                        const char *table_text, size_t table_len, uint32_t minlen, uint32_t maxlen,
+                        uint32_t word_max, uint64_t *keyspace /* nullable */, uint64_t *kept /* nullable */);
+int dwpa_scan_load_table(dwpa_scan *scan, uint64_t first, uint32_t count, void *hip_stream);
 /* Stages 2 and 3 for ESSID group g (PMKs of the loaded batch, then every uncracked line of that ESSID). */
 int dwpa_scan_pbkdf2(dwpa_scan *scan, int group, void *hip_stream);
 int dwpa_scan_verify(dwpa_scan *scan, int group, void *hip_stream);
