@@ -10,7 +10,8 @@ OBJS := $(OBJ)/kernels.o $(OBJ)/rules_dev.o $(OBJ)/engine.o $(OBJ)/m22000_host.o
         $(OBJ)/pbkdf2_module.o $(OBJ)/pbkdf2_hsaco.o $(OBJ)/host_crypto.o $(OBJ)/host_check.o \
         $(OBJ)/mask.o $(OBJ)/mask_dev.o $(OBJ)/crack_common.o $(OBJ)/hybrid_dev.o \
         $(OBJ)/combi_dev.o $(OBJ)/chain.o $(OBJ)/chain_dev.o $(OBJ)/chain_rules_dev.o \
-        $(OBJ)/crack_range.o $(OBJ)/markov.o $(OBJ)/markov_dev.o $(OBJ)/table.o $(OBJ)/table_dev.o
+        $(OBJ)/crack_range.o $(OBJ)/markov.o $(OBJ)/markov_dev.o $(OBJ)/table.o $(OBJ)/table_dev.o \
+        $(OBJ)/assoc.o $(OBJ)/assoc_dev.o
 LLVM := /opt/rocm/lib/llvm/bin
 ISSUE_RULE ?= sched=1:alt:orig:asmnop,before_half
 # 1: the two work-queue PBKDF2 kernels keep their cold words in LDS (pbkdf2_dev.hpp pbkdf2_lane_lds); 0: the plain lane
@@ -70,7 +71,7 @@ oracle:
 	$(MAKE) -s -C oracle
 
 asm: $(SRC)/kernels.hip $(SRC)/mask_dev.hip $(SRC)/hybrid_dev.hip $(SRC)/combi_dev.hip $(SRC)/chain_dev.hip \
-     $(SRC)/chain_rules_dev.hip $(SRC)/rules_dev.hip $(SRC)/markov_dev.hip $(SRC)/table_dev.hip $(HDRS)
+     $(SRC)/chain_rules_dev.hip $(SRC)/rules_dev.hip $(SRC)/markov_dev.hip $(SRC)/table_dev.hip $(SRC)/assoc_dev.hip $(HDRS)
 	@mkdir -p build/asm
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $< -o build/asm/kernels.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/mask_dev.hip -o build/asm/mask_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
@@ -81,6 +82,7 @@ asm: $(SRC)/kernels.hip $(SRC)/mask_dev.hip $(SRC)/hybrid_dev.hip $(SRC)/combi_d
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/rules_dev.hip -o build/asm/rules_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/markov_dev.hip -o build/asm/markov_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/table_dev.hip -o build/asm/table_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
+	$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -Iinclude -c $(SRC)/assoc_dev.hip -o build/asm/assoc_dev.o -save-temps=obj -Rpass-analysis=kernel-resource-usage
 
 clean:
 	rm -rf build $(LIB)
@@ -92,7 +94,7 @@ tools: tools/bin/valu_peak tools/bin/pbkdf2_lab tools/bin/valu_lat tools/bin/val
        tools/bin/inflate_check tools/bin/item_queue_check tools/bin/rules_fuzz_asan tools/bin/clock_idle \
        tools/bin/inflate_check_tsan tools/bin/tail_placement tools/bin/parse_fuzz_asan tools/bin/host_check_fuzz_asan tools/bin/host_pbkdf2_paths tools/bin/vgpr_bank \
        tools/bin/mask_fuzz_asan tools/bin/chain_fuzz_asan tools/bin/range_cursor_check tools/bin/markov_fuzz_asan \
-       tools/bin/table_fuzz_asan
+       tools/bin/table_fuzz_asan tools/bin/assoc_fuzz_asan
 
 tools/bin/valu_lat: tools/valu_lat.hip
 	@mkdir -p tools/bin
@@ -151,6 +153,14 @@ tools/bin/table_fuzz_asan: tools/table_fuzz.cpp $(SRC)/table.cpp $(SRC)/table.hp
 	@mkdir -p tools/bin
 	$(HIPCC) -O1 -g -std=c++17 -Iinclude -I$(SRC) -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
 	    -o $@ tools/table_fuzz.cpp $(SRC)/table.cpp
+
+# the association attack's host side (file parser, single generator, nets, entries, start[], candidates) over the
+# fixtures and random plans under AddressSanitizer + UBSan: assoc.cpp with the rule engine and the line parser
+tools/bin/assoc_fuzz_asan: tools/assoc_fuzz.cpp $(SRC)/assoc.cpp $(SRC)/assoc.hpp $(SRC)/rules.cpp $(SRC)/rules.hpp \
+                           $(SRC)/rules_apply.hpp $(SRC)/dict_reader.hpp $(SRC)/m22000_host.cpp $(SRC)/m22000_host.hpp
+	@mkdir -p tools/bin
+	$(HIPCC) -O1 -g -std=c++17 -Iinclude -I$(SRC) -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
+	    -o $@ tools/assoc_fuzz.cpp $(SRC)/assoc.cpp $(SRC)/rules.cpp $(SRC)/m22000_host.cpp -lz -lpthread
 
 # host fuzz of the chain attack's keyspace / split arithmetic under AddressSanitizer + UBSan: chain.cpp alone
 tools/bin/chain_fuzz_asan: tools/chain_fuzz.cpp $(SRC)/chain.cpp $(SRC)/chain.hpp include/dwpa22000.h

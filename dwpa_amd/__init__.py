@@ -23,15 +23,20 @@ this package is its Python host side:
   combination of per-byte alternatives of every word (``python -m dwpa_amd.table``); :meth:`Scan.set_table` /
   :meth:`Scan.load_table` are its scan-path calls, :func:`table_parse` / :func:`table_builtin` /
   :func:`table_keyspace` / :func:`table_candidates` its host-only helpers
+* :func:`crack_assoc`      -- association attack (hashcat ``-a 9``, ``web/rkg.php``'s per-net pass): every net of the
+  hash file against its own words -- an association file's ``MAC_AP:WORD`` lines, the built-in single generator, rules
+  on top (``python -m dwpa_amd.assoc``); :meth:`Scan.set_assoc` / :meth:`Scan.load_assoc` are its scan-path calls,
+  :func:`assoc_single` / :func:`assoc_plan` / :func:`assoc_candidates` its host-only helpers
 * :mod:`dwpa_amd.help_crack` -- ``run_cracker`` replacement for help_crack.py
 """
-from ._lib import (DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS, DWPA_COMBI_AMP_LEFT,  # noqa: F401
+from ._lib import (DWPA_ASSOC_SINGLE, DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS, DWPA_COMBI_AMP_LEFT,  # noqa: F401
                    DWPA_COMBI_AMP_RIGHT, DWPA_HYBRID_MASK_WORD, DWPA_HYBRID_WORD_MASK, DwpaError, load)
 from .m22000 import (BatchJobs, chain_candidate, chain_keyspace, chain_split, check_batch,  # noqa: F401
                      check_key_m22000, crack_chain, crack_combinator, crack_files, crack_hybrid, crack_mask,
                      device_count, group_by_essid, markov_load, markov_train, mask_candidate, mask_candidates, mask_keyspace, check_stats, hash_m22000, hc_unhex, init,
                      parse_m22000, pbkdf2_pmk, rules_count, rules_count_ex, rules_expand, Scan, crack_table, table_builtin,
-                     table_candidates, table_keyspace, table_parse)
+                     table_candidates, table_keyspace, table_parse, assoc_candidates, assoc_plan, assoc_single,
+                     crack_assoc)
 
 __all__ = ["DwpaError", "load", "BatchJobs", "check_key_m22000", "check_batch", "pbkdf2_pmk", "hc_unhex", "hash_m22000",
            "crack_files", "rules_count", "rules_count_ex", "check_stats", "rules_expand", "device_count", "Scan",
@@ -39,4 +44,5 @@ __all__ = ["DwpaError", "load", "BatchJobs", "check_key_m22000", "check_batch", 
            "crack_hybrid", "DWPA_HYBRID_WORD_MASK", "DWPA_HYBRID_MASK_WORD",
            "crack_combinator", "DWPA_COMBI_AMP_RIGHT", "DWPA_COMBI_AMP_LEFT",
            "crack_chain", "chain_keyspace", "chain_split", "chain_candidate", "DWPA_CHAIN_LIST", "DWPA_CHAIN_MASK",
-           "DWPA_CHAIN_MAX_PARTS", "crack_table", "table_parse", "table_builtin", "table_keyspace", "table_candidates"]
+           "DWPA_CHAIN_MAX_PARTS", "crack_table", "table_parse", "table_builtin", "table_keyspace", "table_candidates",
+           "crack_assoc", "assoc_single", "assoc_plan", "assoc_candidates", "DWPA_ASSOC_SINGLE"]

@@ -25,6 +25,7 @@ DWPA_COMBI_AMP_RIGHT, DWPA_COMBI_AMP_LEFT = 0, 1  # hashcat -a 1: the list held 
 DWPA_CHAIN_LIST, DWPA_CHAIN_MASK, DWPA_CHAIN_MAX_PARTS = 0, 1, 4  # chain attack: the kind of a part, the most parts
 DWPA_MARKOV_BYTES = 4128784  # a Markov model file / image: 16-byte header + 63 x 256 rows of 256 bytes
 DWPA_TABLE_MAX_ALT, DWPA_TABLE_IMAGE_BYTES = 16, 4352  # table attack: alternatives per byte, the parsed table image
+DWPA_ASSOC_SINGLE = 1  # association attack flags: add the single generator's words to every net
 DWPA_DICT_OK, DWPA_DICT_DAMAGED = 0, 1  # dwpa_crack_files_ex per-dictionary status (or DWPA_E_IO)
 DWPA_RULES_DEFAULT, DWPA_RULES_HASHCAT, DWPA_RULES_FULL = 0, 1, 2  # dwpa_config.rule_mode
 DWPA_BACKEND_DEVICE, DWPA_BACKEND_HOST_SMALL, DWPA_BACKEND_HOST_FALLBACK = 0, 1, 2  # dwpa_check_stats.backend
@@ -100,6 +101,11 @@ class Hit(ctypes.Structure):
 class ChainPart(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int), ("d_offsets", ctypes.c_void_p), ("d_bytes", ctypes.c_void_p),
                 ("nwords", ctypes.c_uint64), ("mask", ctypes.c_char_p), ("mask_len", ctypes.c_size_t)]
+
+
+class AssocInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("keyspace", "nets", "entries", "file_lines", "unmatched", "malformed",
+                                               "dropped")] + [("rules", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class ChainSpec(ctypes.Structure):
@@ -216,6 +222,22 @@ SIGNATURES = {
     "dwpa_scan_load_table": ([_P, ctypes.c_uint64, ctypes.c_uint32, _P], ctypes.c_int),
     "dwpa_crack_table": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64,
                           ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)], ctypes.c_int),
+    "dwpa_assoc_single": ([ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, _P, ctypes.c_size_t,
+                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                           ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dwpa_assoc_plan": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,
+                         ctypes.POINTER(AssocInfo)], ctypes.c_int),
+    "dwpa_assoc_candidates": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,
+                               ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t, _P, ctypes.POINTER(ctypes.c_uint32),
+                               ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+    "dwpa_scan_num_nets": ([_P], ctypes.c_int),
+    "dwpa_scan_net_of_line": ([_P, ctypes.c_size_t], ctypes.c_int64),
+    "dwpa_scan_set_assoc": ([_P, ctypes.POINTER(Bytes), ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
+                             ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                             ctypes.POINTER(ctypes.c_uint64)], ctypes.c_int),
+    "dwpa_scan_load_assoc": ([_P, ctypes.c_uint64, ctypes.c_uint32, _P], ctypes.c_int),
+    "dwpa_crack_assoc": ([ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64,
+                          ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(Config)], ctypes.c_int),
     "dwpa_scan_pbkdf2": ([_P, ctypes.c_int, _P], ctypes.c_int),
     "dwpa_scan_verify": ([_P, ctypes.c_int, _P], ctypes.c_int),
     "dwpa_scan_run": ([_P, _P], ctypes.c_int),
@@ -238,6 +260,8 @@ SIGNATURES = {
     "dwpa_debug_check_hit_records": ([ctypes.c_int], ctypes.c_uint64),  # test hook, not in include/dwpa22000.h
     "dwpa_debug_scan_work": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_int], None),  # test hook, not in the header
     "dwpa_debug_crack_loads": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_int], None),  # test hook, not in the header
+    "dwpa_debug_assoc_work": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_int], None),  # test hook, not in the header
+    "dwpa_debug_assoc_segcap": ([ctypes.c_uint32], ctypes.c_uint32),  # test hook, not in the header
 }
 
 # Bit i of dwpa_debug_pbkdf2_kernels' mask (csrc/kernels.hpp Pbkdf2Kernel): the hipcc-scheduled kernels of kernels.hip,
@@ -316,6 +340,24 @@ def crack_loads(reset: bool = False) -> dict:
     out = (ctypes.c_uint64 * 4)()
     load().dwpa_debug_crack_loads(out, 1 if reset else 0)
     return dict(zip(CRACK_LOAD_NAMES, (int(v) for v in out)))
+
+
+ASSOC_WORK_NAMES = ("slots_derived", "segments")
+
+
+def assoc_work(reset: bool = False) -> dict:
+    """What association runs (dwpa_scan_run after load_assoc) have launched in this process since the last reset (test
+    hook): slots derived -- one PBKDF2 each -- and segments handed to the verify kernels.  A net whose lines are all
+    retired adds to neither."""
+    out = (ctypes.c_uint64 * 2)()
+    load().dwpa_debug_assoc_work(out, 1 if reset else 0)
+    return dict(zip(ASSOC_WORK_NAMES, (int(v) for v in out)))
+
+
+def assoc_segcap(records: int = 0) -> int:
+    """Set the number of records a scan's segment lists start with (test hook; 0: the default); returns the previous
+    setting.  A list that is too short is grown and its load repeated."""
+    return int(load().dwpa_debug_assoc_segcap(int(records)))
 
 
 def check(rc: int, what: str = "") -> int:

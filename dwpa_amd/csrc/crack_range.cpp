@@ -13,6 +13,9 @@
 //   dwpa_crack_table(): one word list under a substitution table (table.hpp): every combination of the per-byte
 //                       alternatives of every kept word.  The keyspace is a prefix sum over the words; one segment
 //                       of raw indices [skip, skip + limit).
+//   dwpa_crack_assoc(): every net (ESSID, MAC_AP) of the hash file against its own words x the rules (assoc.hpp): the
+//                       keyspace is a prefix sum over the nets; one segment of raw indices [skip, skip + limit).  The
+//                       host-only dwpa_assoc_single / _plan / _candidates share its set-up and live here with it.
 //
 // There is no dictionary feed, so none of crack.cpp's reader / item-queue machinery: every worker --
 // DWPA_CRACK_SHARDS_PER_DEVICE per selected device -- takes batch-sized ascending index ranges from one shared cursor
@@ -38,6 +41,7 @@
 #include <vector>
 
 #include "dwpa22000.h"
+#include "assoc.hpp"
 #include "chain.hpp"
 #include "crack_common.hpp"
 #include "crack_cursor.hpp"
@@ -581,9 +585,181 @@ int crack_table_impl(const char* hash_file, const char* dict, const char* table_
     return crack_range(call, hash_file, nec, out_file, cfg, std::move(segs), *attack);
 }
 
+// The association attack (assoc.hpp): the plan -- nets, entries, start[] -- is built on the host from the parsed hash
+// file before any device is touched; it names the keyspace and rebuilds a hit's PSK.  Every worker's scan takes the
+// entries (scan_set_assoc) and builds its own index over its own nets; the two must agree on K.
+struct AssocAttack {
+    AssocPlan plan;
+    std::unique_ptr<RuleSet> rules;
+
+    struct Worker {
+        const AssocAttack& at;
+        explicit Worker(const AssocAttack& a) : at(a) {}
+        int open(ScanWorker& w) {
+            const AssocPlan& p = at.plan;
+            if (scan_num_nets(w.scan) != p.nets.nets.size()) return DWPA_E_HIP;
+            std::vector<dwpa_bytes> words((size_t)p.entries());
+            for (size_t e = 0; e < words.size(); e++)
+                words[e] = dwpa_bytes{(const uint8_t*)p.wbytes.data() + p.woff[e], (size_t)(p.woff[e + 1] - p.woff[e])};
+            uint64_t K = 0;
+            const int r = scan_set_assoc(w.scan, words.data(), p.wnet.data(), words.size(), at.rules.get(), 8, 63, &K);
+            if (r < 0) return r;
+            return K == p.keyspace() ? 0 : DWPA_E_HIP;
+        }
+        int enter(ScanWorker&, size_t) { return 0; }
+        int load(ScanWorker& w, uint64_t first, uint32_t count) { return scan_load_assoc(w.scan, first, count, w.stream); }
+        int counted(ScanWorker& w, uint32_t, uint64_t* n) {
+            uint32_t kept = 0;  // the stream is idle by now: this copy waits for nothing
+            const int r = scan_counter_raw(w.scan, w.stream, &kept);
+            *n = std::min(kept, scan_batch_cap(w.scan));
+            return r;
+        }
+        bool plain_of(uint64_t id, std::string* psk) const { return at.plan.candidate(id, psk); }
+    };
+};
+
+// The hash file parsed, the rules file loaded under the process's rule mode and the plan built: what dwpa_assoc_plan,
+// dwpa_assoc_candidates and dwpa_crack_assoc share.  A negative DWPA_E_* after one stderr line, else 0.
+int assoc_prepare(const char* hash_file, const char* assoc_file, uint32_t flags, const char* rules_file, int rule_mode,
+                  AssocAttack* at) {
+    if (!hash_file || (flags & ~DWPA_ASSOC_SINGLE) || (!assoc_file && !(flags & DWPA_ASSOC_SINGLE))) {
+        fprintf(stderr, "[dwpa] the association attack takes an association file, the single generator, or both\n");
+        return DWPA_E_ARG;
+    }
+    if (rule_mode != DWPA_RULES_DEFAULT && rule_mode != DWPA_RULES_HASHCAT && rule_mode != DWPA_RULES_FULL)
+        return DWPA_E_ARG;
+    if (rules_file) {
+        at->rules = std::make_unique<RuleSet>();
+        at->rules->mode = rule_mode == DWPA_RULES_DEFAULT ? engine_rule_mode() : rule_mode;
+        const int lr = at->rules->load_file(rules_file);
+        if (lr == DWPA_E_IO) fprintf(stderr, "[dwpa] rules %s: cannot be opened\n", rules_file);
+        if (lr < 0) return lr;
+    }
+    std::vector<std::string> lines;
+    if (!read_hash_file(hash_file, lines)) {
+        fprintf(stderr, "[dwpa] hash file %s: cannot be opened\n", hash_file);
+        return DWPA_E_IO;
+    }
+    std::vector<ParsedLine> parsed(lines.size());
+    for (size_t i = 0; i < lines.size(); i++) parsed[i] = parse_m22000(lines[i].data(), lines[i].size());
+    const int r = assoc_plan(parsed, assoc_file, (flags & DWPA_ASSOC_SINGLE) != 0, rules_file ? 1u : 8u, at->rules.get(),
+                             &at->plan);
+    if (r == DWPA_E_IO) fprintf(stderr, "[dwpa] association file %s: cannot be read\n", assoc_file);
+    else if (r < 0)
+        fprintf(stderr, "[dwpa] the association attack's keyspace is above 2^64 - 1, or one net has 2^32 or more "
+                        "word x rule choices\n");
+    return r;
+}
+
+int crack_assoc_impl(const char* hash_file, const char* assoc_file, uint32_t flags, const char* rules_file,
+                     uint64_t skip, uint64_t limit, int nec, const char* out_file, const dwpa_config* cfg) {
+    CrackCall call;
+    if (!hash_file || !out_file) return DWPA_RC_ERROR;
+    if (!crack_check_args(cfg, nec)) return DWPA_RC_ERROR;
+    auto attack = std::make_unique<AssocAttack>();
+    const int pr = assoc_prepare(hash_file, assoc_file, flags, rules_file,
+                                 DWPA_CFG_HAS(cfg, rule_mode) ? cfg->rule_mode : DWPA_RULES_DEFAULT, attack.get());
+    if (attack->rules) {
+        call.st.rules = (uint32_t)attack->rules->size();
+        call.st.rules_skipped = (uint32_t)attack->rules->skipped.size();
+        call.st.rules_rejmem = attack->rules->rejmem;
+        crack_publish_stats(call.st, {});
+    }
+    if (pr < 0) return DWPA_RC_ERROR;
+    const AssocPlan& p = attack->plan;
+    call.st.words = p.entries();
+    fprintf(stderr, "[dwpa] association attack: %llu nets, %llu entries, %u rules; association file: %llu lines, %llu "
+                    "unmatched, %llu malformed; %llu words dropped\n", (unsigned long long)p.nets.nets.size(),
+            (unsigned long long)p.entries(), p.R, (unsigned long long)p.file_lines, (unsigned long long)p.unmatched,
+            (unsigned long long)p.malformed, (unsigned long long)p.dropped);
+    const uint64_t K = p.keyspace();
+    if (K > 0 && skip >= K) {
+        fprintf(stderr, "[dwpa] --skip is not below the keyspace\n");
+        return DWPA_RC_ERROR;
+    }
+    std::vector<RangeSegment> segs;  // K = 0 (no net has a word): nothing to run, the call exhausts
+    if (K > 0) {
+        const uint64_t room = K - skip;
+        segs.push_back(RangeSegment{skip, skip + (limit && limit < room ? limit : room)});
+    }
+    return crack_range(call, hash_file, nec, out_file, cfg, std::move(segs), *attack);
+}
+
 }  // namespace
 
 }  // namespace dwpa
+
+extern "C" int dwpa_assoc_single(const char* line, size_t line_len, uint32_t minlen, uint8_t* out, size_t out_cap,
+                                 uint32_t* lens, size_t lens_cap, size_t* nwords, size_t* nbytes) {
+    return dwpa::guarded([&]() -> int {
+        if (!line || !nwords || !nbytes) return DWPA_E_ARG;
+        const dwpa::ParsedLine p = dwpa::parse_m22000(line, line_len);
+        if (p.status) return p.status;
+        std::vector<std::string> words;
+        dwpa::assoc_single(p.mac_ap, p.essid, minlen, &words);
+        size_t total = 0;
+        for (const std::string& w : words) total += w.size();
+        *nwords = words.size();
+        *nbytes = total;
+        if (words.size() > lens_cap || total > out_cap || (words.size() && (!out || !lens))) return DWPA_E_OVERFLOW;
+        size_t at = 0;
+        for (size_t k = 0; k < words.size(); k++) {
+            memcpy(out + at, words[k].data(), words[k].size());
+            at += words[k].size();
+            lens[k] = (uint32_t)words[k].size();
+        }
+        return 0;
+    });
+}
+
+extern "C" int dwpa_assoc_plan(const char* hash_file, const char* assoc_file, uint32_t flags, const char* rules_file,
+                               dwpa_assoc_info* out) {
+    return dwpa::guarded([&]() -> int {
+        if (!out) return DWPA_E_ARG;
+        dwpa::AssocAttack at;
+        const int r = dwpa::assoc_prepare(hash_file, assoc_file, flags, rules_file, DWPA_RULES_DEFAULT, &at);
+        if (r < 0) return r;
+        const dwpa::AssocPlan& p = at.plan;
+        *out = dwpa_assoc_info{p.keyspace(), p.nets.nets.size(), p.entries(), p.file_lines, p.unmatched, p.malformed,
+                               p.dropped, p.R, 0};
+        return 0;
+    });
+}
+
+extern "C" int dwpa_assoc_candidates(const char* hash_file, const char* assoc_file, uint32_t flags,
+                                     const char* rules_file, const uint64_t* indices, size_t n, uint8_t* out,
+                                     uint32_t* out_len, uint32_t* first_line) {
+    return dwpa::guarded([&]() -> int {
+        if (n && (!indices || !out || !out_len)) return DWPA_E_ARG;
+        dwpa::AssocAttack at;
+        const int r = dwpa::assoc_prepare(hash_file, assoc_file, flags, rules_file, DWPA_RULES_DEFAULT, &at);
+        if (r < 0) return r;
+        const dwpa::AssocPlan& p = at.plan;
+        std::string c;
+        for (size_t k = 0; k < n; k++) {
+            if (indices[k] >= p.keyspace()) return DWPA_E_ARG;
+            size_t net = 0;
+            memset(out + 64 * k, 0, 64);
+            if (p.candidate(indices[k], &c, &net)) {
+                memcpy(out + 64 * k, c.data(), c.size());
+                out_len[k] = (uint32_t)c.size();
+            } else {
+                out_len[k] = 0xffffffffu;
+            }
+            if (first_line) first_line[k] = p.nets.nets[net].lines[0];
+        }
+        return 0;
+    });
+}
+
+extern "C" int dwpa_crack_assoc(const char* hash_file, const char* assoc_file, uint32_t flags, const char* rules_file,
+                                uint64_t skip, uint64_t limit, int nonce_error_corrections, const char* out_file,
+                                const dwpa_config* cfg) {
+    return dwpa::guarded([&]() -> int {
+        return dwpa::crack_assoc_impl(hash_file, assoc_file, flags, rules_file, skip, limit, nonce_error_corrections,
+                                      out_file, cfg);
+    }, DWPA_RC_ERROR, DWPA_RC_ERROR);
+}
 
 extern "C" int dwpa_crack_table(const char* hash_file, const char* dict, const char* table_file, uint32_t word_max,
                                 uint64_t skip, uint64_t limit, int nonce_error_corrections, const char* out_file,

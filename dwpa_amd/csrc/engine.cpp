@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "dwpa22000.h"
+#include "assoc.hpp"
 #include "engine.hpp"
 #include "kernels.hpp"
 #include "m22000_host.hpp"
@@ -1517,6 +1518,24 @@ struct dwpa_scan {
     uint64_t table_keyspace = 0;
     uint32_t table_nkept = 0;
     dwpa::DevBuf table_tab, table_start, table_kword;
+    // The nets (assoc.hpp): per input line its net (-1: not usable), per net its ESSID group and its table lines.
+    struct Net {
+        uint32_t group = 0;
+        std::vector<uint32_t> lines;  // table lines
+    };
+    std::vector<int32_t> net_of_input;
+    std::vector<Net> nets;
+    // dwpa_scan_set_assoc: the scan owns the entries, the index over the nets that own indices, one salt entry per
+    // ESSID group, the rule image, the per-slot salt references and the four segment lists.  assoc_loaded: the batch
+    // holds an association load (scan_run dispatches on it; every other load clears it).  assoc_dirty: the per-net
+    // live-line arrays are behind the retired set, as mg_dirty says of the multi-group tables.
+    bool assoc_set = false, assoc_loaded = false, assoc_dirty = true;
+    uint64_t assoc_keyspace = 0, assoc_first = 0;
+    uint32_t assoc_nidx = 0, assoc_count = 0, assoc_minlen = 8, assoc_maxlen = 63;
+    dwpa::DevRules assoc_rules;
+    dwpa::DevBuf assoc_start, assoc_ent, assoc_woff, assoc_wbytes, assoc_salt, assoc_sref, assoc_nloff, assoc_nline;
+    dwpa::DevBuf assoc_seg[4];
+    uint32_t assoc_segcap[4] = {0, 0, 0, 0};
 };
 
 namespace dwpa {
@@ -1562,6 +1581,18 @@ int scan_create(int device, const char* const* lines, const size_t* lens, size_t
         salts.insert(salts.end(), sb.begin(), sb.end());
         sc->groups.push_back(g);
     }
+    {
+        AssocNets an;
+        assoc_nets(parsed, &an);
+        std::map<std::string, uint32_t> group_of;
+        for (size_t g = 0; g < sc->groups.size(); g++) group_of[sc->groups[g].essid] = (uint32_t)g;
+        sc->net_of_input = an.net_of_line;
+        sc->nets.resize(an.nets.size());
+        for (size_t n = 0; n < an.nets.size(); n++) {
+            sc->nets[n].group = group_of[an.nets[n].essid];
+            for (uint32_t i : an.nets[n].lines) sc->nets[n].lines.push_back(sc->line_of[i]);
+        }
+    }
     sc->cracked.assign(sc->tb.lines.size(), 0);
     for (size_t l = 0; l < sc->tb.never.size(); l++)
         if (sc->tb.never[l]) sc->cracked[l] = 1;  // can never match: never verified
@@ -1588,6 +1619,10 @@ void scan_destroy(dwpa_scan* sc) {
     sc->mask_tab.release();
     sc->markov_tab.release();
     sc->table_tab.release(); sc->table_start.release(); sc->table_kword.release();
+    sc->assoc_start.release(); sc->assoc_ent.release(); sc->assoc_woff.release(); sc->assoc_wbytes.release();
+    sc->assoc_salt.release(); sc->assoc_sref.release(); sc->assoc_nloff.release(); sc->assoc_nline.release();
+    for (auto& b : sc->assoc_seg) b.release();
+    rules_release(&sc->assoc_rules);
     for (auto& cp : sc->chain) {
         cp.tab.release();
         rules_release(&cp.rules);
@@ -1602,6 +1637,7 @@ int scan_load_dict(dwpa_scan* sc, const uint64_t* off, const uint8_t* bytes, uin
     if (!sc || count > (fill ? 16 * (uint64_t)sc->batch_cap : sc->batch_cap)) return DWPA_E_ARG;
     HIPCHK(hipSetDevice(sc->device));
     hipStream_t s = as_stream(stream);
+    sc->assoc_loaded = false;
     HIPCHK(hipMemsetAsync(sc->batch.counters.p, 0, 4, s));
     HIPCHK(launch_prep_dict(off, bytes, first, count, minlen, maxlen, (uint32_t*)sc->batch.mid.p,
                             (uint64_t*)sc->batch.ids.p, (uint32_t*)sc->batch.counters.p, sc->batch_cap, true, s));
@@ -1620,6 +1656,7 @@ int scan_load_numeric(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t di
     if (!sc || count > sc->batch_cap || digits == 0 || digits > 20) return DWPA_E_ARG;
     HIPCHK(hipSetDevice(sc->device));
     hipStream_t s = as_stream(stream);
+    sc->assoc_loaded = false;
     HIPCHK(hipMemcpyAsync(sc->batch.counters.p, &count, 4, hipMemcpyHostToDevice, s));
     HIPCHK(launch_prep_numeric(first, count, digits, (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
                                sc->batch_cap, s));
@@ -1668,6 +1705,7 @@ static int scan_load_markov(dwpa_scan* sc, uint64_t first, uint32_t count, void*
     HIPCHK(hipSetDevice(sc->device));
     uint8_t digits[64];
     markov_digits(*sc->markov, first < K ? first : 0, digits);  // first == K only with count 0
+    sc->assoc_loaded = false;
     HIPCHK(launch_prep_markov(digits, first, count, sc->markov->npos, (const uint8_t*)sc->markov_tab.p,
                               (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
                               (uint32_t*)sc->batch.counters.p, sc->batch_cap, as_stream(stream)));
@@ -1683,6 +1721,7 @@ int scan_load_mask(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream) 
     HIPCHK(hipSetDevice(sc->device));
     uint8_t digits[64];
     mask_digits(sc->mask, first < K ? first : 0, digits);  // first == K only with count 0: nothing is generated
+    sc->assoc_loaded = false;
     HIPCHK(launch_prep_mask(digits, first, count, sc->mask.npos, (const uint8_t*)sc->mask_tab.p,
                             (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p, (uint32_t*)sc->batch.counters.p,
                             sc->batch_cap, as_stream(stream)));
@@ -1737,6 +1776,7 @@ int scan_load_table(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream)
     const uint64_t K = sc->table_keyspace;
     if (first > K || count > K - first) return DWPA_E_ARG;  // first + count > K, also when the sum wraps
     HIPCHK(hipSetDevice(sc->device));
+    sc->assoc_loaded = false;
     HIPCHK(launch_prep_table(first, count, sc->table_nkept, (const uint64_t*)sc->table_start.p,
                              (const uint32_t*)sc->table_kword.p, sc->table_off, sc->table_bytes,
                              (const uint8_t*)sc->table_tab.p, (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
@@ -1763,6 +1803,7 @@ int scan_load_hybrid(dwpa_scan* sc, const uint64_t* off, const uint8_t* bytes, u
     HIPCHK(hipMemsetAsync(sc->batch.counters.p, 0, 4, s));
     uint8_t digits[64];
     mask_digits(sc->mask, mask_first < K ? mask_first : 0, digits);  // mask_first == K only with mask_count 0
+    sc->assoc_loaded = false;
     HIPCHK(launch_prep_hybrid(digits, off, bytes, first_word, nwords, mask_first, mask_count, K, sc->mask.npos,
                               mode == DWPA_HYBRID_MASK_WORD, minlen, maxlen, (const uint8_t*)sc->mask_tab.p,
                               (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
@@ -1790,6 +1831,7 @@ int scan_load_combinator(dwpa_scan* sc, const uint64_t* base_off, const uint8_t*
     HIPCHK(hipSetDevice(sc->device));
     hipStream_t s = as_stream(stream);
     HIPCHK(hipMemsetAsync(sc->batch.counters.p, 0, 4, s));
+    sc->assoc_loaded = false;
     HIPCHK(launch_prep_combinator(base_off, base_bytes, first_base, nbase, amp_off, amp_bytes, amp_words, amp_first,
                                   amp_count, amp_side == DWPA_COMBI_AMP_LEFT, minlen, maxlen,
                                   (uint32_t*)sc->batch.mid.p, (uint64_t*)sc->batch.ids.p,
@@ -1887,6 +1929,7 @@ int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minl
     if (first > K || count > K - first) return DWPA_E_ARG;  // first + count > K, also when the sum wraps
     HIPCHK(hipSetDevice(sc->device));
     hipStream_t s = as_stream(stream);
+    sc->assoc_loaded = false;
     HIPCHK(hipMemsetAsync(sc->batch.counters.p, 0, 4, s));
     if (count == 0) return 0;  // first == K, or K == 0, only with count 0: nothing is generated
     ChainPartLaunch lp[CHAIN_MAX_PARTS];
@@ -1920,12 +1963,201 @@ int scan_load_chain(dwpa_scan* sc, uint64_t first, uint32_t count, uint32_t minl
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// the association attack (assoc_dev.hip)
+// ---------------------------------------------------------------------------------------------------------
+uint32_t scan_num_nets(const dwpa_scan* sc) { return (uint32_t)sc->nets.size(); }
+int64_t scan_net_of_line(const dwpa_scan* sc, size_t input_line) {
+    if (input_line >= sc->net_of_input.size() || sc->net_of_input[input_line] < 0) return DWPA_E_ARG;
+    return sc->net_of_input[input_line];
+}
+
+// Segment records a list starts with (dwpa_debug_assoc_segcap, a test hook; 0: a share of the batch).  A list that
+// turns out too short is grown and its load repeated, so the figure only decides how often that happens.
+static std::atomic<uint32_t> g_assoc_segcap{0};
+// Slots derived and segments verified by association runs (dwpa_debug_assoc_work, a test hook): a retired net adds to
+// neither.
+static std::atomic<uint64_t> g_assoc_slots{0}, g_assoc_segs{0};
+
+// Everything is checked and built on the host and uploaded into buffers of this call's own; the scan changes only when
+// nothing can fail any more.  Launches that still read the old association are waited for first.
+int scan_set_assoc(dwpa_scan* sc, const dwpa_bytes* words, const uint32_t* net_of_word, size_t count, const RuleSet* rs,
+                   uint32_t minlen, uint32_t maxlen, uint64_t* keyspace) {
+    if (!sc || count > UINT32_MAX || (count && (!words || !net_of_word)) || (rs && rs->size() == 0) ||
+        (rs && rs->size() > UINT32_MAX))
+        return DWPA_E_ARG;
+    const uint32_t R = rs ? (uint32_t)rs->size() : 1u;
+    const size_t nnets = sc->nets.size();
+    std::vector<uint64_t> woff(1, 0);
+    std::vector<uint8_t> wbytes;
+    std::vector<uint32_t> wcount(nnets, 0), wfirst(nnets, 0);
+    for (size_t i = 0; i < count; i++) {
+        const uint32_t n = net_of_word[i];
+        if (n >= nnets || (i && n < net_of_word[i - 1]) || !words[i].ptr || words[i].len < 1 ||
+            words[i].len > ASSOC_WORD_MAX)
+            return DWPA_E_ARG;
+        if (!wcount[n]++) wfirst[n] = (uint32_t)i;
+        wbytes.insert(wbytes.end(), (const uint8_t*)words[i].ptr, (const uint8_t*)words[i].ptr + words[i].len);
+        woff.push_back(wbytes.size());
+    }
+    wbytes.resize(wbytes.size() + 64, 0);  // load_key_block reads whole dwords
+    // one salt entry per ESSID group, in launch_pbkdf2_ms' format
+    std::vector<uint32_t> salt, sref_of_group, sb;
+    for (const ScanGroup& g : sc->groups) {
+        sb.clear();
+        const uint32_t nb = build_salt_blocks(g.essid, sb);
+        sref_of_group.push_back((uint32_t)salt.size());
+        salt.push_back(nb);
+        salt.insert(salt.end(), sb.begin(), sb.end());
+    }
+    std::vector<uint64_t> start(1, 0);
+    std::vector<AssocEntry> ent;
+    uint64_t K = 0;
+    for (size_t n = 0; n < nnets; n++) {
+        const uint64_t own = (uint64_t)wcount[n] * R;
+        if (own > UINT32_MAX || __builtin_add_overflow(K, own, &K)) return DWPA_E_ARG;
+        if (!own) continue;
+        ent.push_back(AssocEntry{wfirst[n], wcount[n], (uint32_t)n, sref_of_group[sc->nets[n].group]});
+        start.push_back(K);
+    }
+    HIPCHK(hipSetDevice(sc->device));
+    DevBuf b_start, b_ent, b_woff, b_wbytes, b_salt;
+    DevRules dev;
+    auto drop = [&](int r) {
+        b_start.release(); b_ent.release(); b_woff.release(); b_wbytes.release(); b_salt.release();
+        rules_release(&dev);
+        return r;
+    };
+    int r;
+    if ((r = upload(b_start, start, nullptr)) < 0 || (r = upload(b_ent, ent, nullptr)) < 0 ||
+        (r = upload(b_woff, woff, nullptr)) < 0 || (r = upload(b_wbytes, wbytes, nullptr)) < 0 ||
+        (r = upload(b_salt, salt, nullptr)) < 0 || (rs && (r = rules_upload(sc->device, *rs, &dev)) < 0) ||
+        (r = sc->assoc_sref.ensure((size_t)sc->batch_cap * 4)) < 0)
+        return drop(r);
+    if (hipDeviceSynchronize() != hipSuccess) return drop(DWPA_E_HIP);  // the uploads, and what reads the old buffers
+    std::swap(sc->assoc_start, b_start);
+    std::swap(sc->assoc_ent, b_ent);
+    std::swap(sc->assoc_woff, b_woff);
+    std::swap(sc->assoc_wbytes, b_wbytes);
+    std::swap(sc->assoc_salt, b_salt);
+    std::swap(sc->assoc_rules, dev);
+    sc->assoc_nidx = (uint32_t)ent.size();
+    sc->assoc_keyspace = K;
+    sc->assoc_minlen = minlen;
+    sc->assoc_maxlen = std::min<uint32_t>(maxlen, 63);
+    sc->assoc_set = true;
+    sc->assoc_loaded = false;
+    sc->assoc_dirty = true;
+    if (keyspace) *keyspace = K;
+    return drop(0);  // the previous association's buffers
+}
+
+// The live lines of every net, for the generator to cut its segments from: rebuilt when the retired set changed.
+static int scan_assoc_rebuild(dwpa_scan* sc, hipStream_t s) {
+    HIPCHK(hipStreamSynchronize(s));  // the previous arrays may still be read by a queued launch
+    std::vector<uint32_t> off(1, 0), list;
+    for (const dwpa_scan::Net& n : sc->nets) {
+        for (uint32_t l : n.lines) {
+            if (sc->cracked[l]) continue;
+            const uint32_t vc = verify_class(sc->tb.lines[l]);
+            list.push_back(l | (vc == VC_PMKID ? 0u : vc == VC_KV1 ? 1u : vc == VC_KV2 ? 2u : 3u) << 30);
+        }
+        off.push_back((uint32_t)list.size());
+    }
+    RCHK(upload(sc->assoc_nloff, off, s));
+    RCHK(upload(sc->assoc_nline, list, s));
+    HIPCHK(hipStreamSynchronize(s));  // the vectors end with this frame
+    sc->assoc_dirty = false;
+    return 0;
+}
+
+int scan_load_assoc(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream) {
+    if (!sc || !sc->assoc_set || count > sc->batch_cap || sc->tb.lines.size() >= (1u << 30)) return DWPA_E_ARG;
+    const uint64_t K = sc->assoc_keyspace;
+    if (first > K || count > K - first) return DWPA_E_ARG;  // first + count > K, also when the sum wraps
+    HIPCHK(hipSetDevice(sc->device));
+    hipStream_t s = as_stream(stream);
+    if (sc->assoc_dirty) RCHK(scan_assoc_rebuild(sc, s));
+    for (int c = 0; c < 4; c++)
+        if (!sc->assoc_segcap[c]) {
+            const uint32_t hook = g_assoc_segcap.load(std::memory_order_relaxed);
+            const uint32_t want = hook ? hook : std::max<uint32_t>(4096, sc->batch_cap / 16);
+            RCHK(sc->assoc_seg[c].ensure((size_t)want * sizeof(SegDev)));
+            sc->assoc_segcap[c] = want;
+        }
+    uint32_t* ctr = (uint32_t*)sc->batch.counters.p;  // [0] slots, [4..8) the four segment counts
+    HIPCHK(hipMemsetAsync(ctr, 0, 4, s));
+    HIPCHK(hipMemsetAsync(ctr + 4, 0, 16, s));
+    sc->assoc_first = first;
+    sc->assoc_count = count;
+    sc->assoc_loaded = true;
+    AssocLaunch a;
+    a.nidx = sc->assoc_nidx;
+    a.start = (const uint64_t*)sc->assoc_start.p;
+    a.ent = (const AssocEntry*)sc->assoc_ent.p;
+    a.woff = (const uint64_t*)sc->assoc_woff.p;
+    a.wbytes = (const uint8_t*)sc->assoc_wbytes.p;
+    a.roffs = (const uint32_t*)sc->assoc_rules.offs;
+    a.rcode = (const uint32_t*)sc->assoc_rules.code;
+    a.nrules = sc->assoc_rules.nrules;
+    a.net_line_off = (const uint32_t*)sc->assoc_nloff.p;
+    a.net_line = (const uint32_t*)sc->assoc_nline.p;
+    SegDev* seg[4];
+    for (int c = 0; c < 4; c++) seg[c] = (SegDev*)sc->assoc_seg[c].p;
+    HIPCHK(launch_prep_assoc(a, first, count, sc->assoc_minlen, sc->assoc_maxlen, (uint32_t*)sc->batch.mid.p,
+                             (uint64_t*)sc->batch.ids.p, (uint32_t*)sc->assoc_sref.p, ctr, sc->batch_cap, seg,
+                             sc->assoc_segcap, ctr + 4, s));
+    return 0;
+}
+
+// An association load: the slot count and the four segment counts come back in one copy; a list that was too short
+// is grown and the load repeated (the slots it writes are the same), as is a load made before lines were retired.
+// Then one per-slot-salt PBKDF2 over the kept slots and one explicit-segment verify per non-empty class.
+static int scan_run_assoc(dwpa_scan* sc, hipStream_t s) {
+    const uint32_t cap = sc->batch_cap;
+    uint32_t c[8];
+    for (int pass = 0;; pass++) {
+        if (sc->assoc_dirty) RCHK(scan_load_assoc(sc, sc->assoc_first, sc->assoc_count, s));
+        HIPCHK(hipMemcpyAsync(c, sc->batch.counters.p, 32, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        bool grown = false;
+        for (int k = 0; k < 4; k++)
+            if (c[4 + k] > sc->assoc_segcap[k]) {
+                uint32_t want = sc->assoc_segcap[k];
+                while (want < c[4 + k]) want = want > UINT32_MAX / 2 ? UINT32_MAX : want * 2;
+                sc->assoc_seg[k].release();  // nothing reads it: the stream is idle
+                sc->assoc_segcap[k] = 0;
+                RCHK(sc->assoc_seg[k].ensure((size_t)want * sizeof(SegDev)));
+                sc->assoc_segcap[k] = want;
+                grown = true;
+            }
+        if (!grown) break;
+        if (pass >= 2) return DWPA_E_HIP;  // the same load counts the same segments: cannot happen
+        RCHK(scan_load_assoc(sc, sc->assoc_first, sc->assoc_count, s));
+    }
+    const uint32_t n = std::min(c[0], cap);
+    if (n == 0) return 0;
+    HIPCHK(launch_pbkdf2_ms((const uint32_t*)sc->batch.mid.p, cap, n, (const uint32_t*)sc->assoc_salt.p,
+                            (const uint32_t*)sc->assoc_sref.p, (uint32_t*)sc->batch.pmk.p, s));
+    g_assoc_slots.fetch_add(n, std::memory_order_relaxed);
+    for (uint32_t k = 0; k < 4; k++) {
+        if (!c[4 + k]) continue;
+        HIPCHK(launch_verify((const uint32_t*)sc->batch.pmk.p, cap, (const uint64_t*)sc->batch.ids.p,
+                             (const uint32_t*)sc->batch.counters.p, (const SegDev*)sc->assoc_seg[k].p, c[4 + k], 0, 1,
+                             (const LineDev*)sc->lines.p, (const uint32_t*)sc->pool.p, (const AttDev*)sc->atts.p,
+                             (HitDev*)sc->batch.hits.p, (uint32_t*)sc->batch.counters.p + 1, sc->batch.hitcap, 1u << k,
+                             s));
+        g_assoc_segs.fetch_add(c[4 + k], std::memory_order_relaxed);
+    }
+    return 0;
+}
+
 // What the scan path has launched in this process (dwpa_debug_scan_work, a test hook): ESSID groups derived (a fully
 // cracked group costs no PBKDF2), multi-group PBKDF2 launches, and line rows handed to the verifier.
 static std::atomic<uint64_t> g_scan_groups_derived{0}, g_scan_mg_launches{0}, g_scan_line_rows{0};
 
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream) {
-    if (!sc || group < 0 || group >= (int)sc->groups.size()) return DWPA_E_ARG;
+    if (!sc || group < 0 || group >= (int)sc->groups.size() || sc->assoc_loaded) return DWPA_E_ARG;
     HIPCHK(hipSetDevice(sc->device));
     const ScanGroup& g = sc->groups[group];
     bool any = false;
@@ -1939,7 +2171,7 @@ int scan_pbkdf2(dwpa_scan* sc, int group, void* stream) {
 }
 
 int scan_verify(dwpa_scan* sc, int group, void* stream) {
-    if (!sc || group < 0 || group >= (int)sc->groups.size()) return DWPA_E_ARG;
+    if (!sc || group < 0 || group >= (int)sc->groups.size() || sc->assoc_loaded) return DWPA_E_ARG;
     HIPCHK(hipSetDevice(sc->device));
     const ScanGroup& g = sc->groups[group];
     const uint32_t nsegs = sc->batch_cap / 64;
@@ -2020,6 +2252,7 @@ int scan_run(dwpa_scan* sc, void* stream) {
     if (!sc) return DWPA_E_ARG;
     HIPCHK(hipSetDevice(sc->device));
     hipStream_t s = as_stream(stream);
+    if (sc->assoc_loaded) return scan_run_assoc(sc, s);  // what was loaded last decides
     if (sc->mg_dirty) RCHK(scan_mg_rebuild(sc, s));
     const uint32_t cap = sc->batch_cap;
     const uint32_t pstride = sc->mg_stride;
@@ -2086,10 +2319,15 @@ void scan_mark_cracked(dwpa_scan* sc, uint32_t input_line) {
     if (input_line < sc->status.size() && sc->status[input_line] == 0 && !sc->cracked[sc->line_of[input_line]]) {
         sc->cracked[sc->line_of[input_line]] = 1;
         sc->mg_dirty = true;
+        sc->assoc_dirty = true;
     }
 }
 uint32_t scan_batch_cap(const dwpa_scan* sc) { return sc->batch_cap; }
-Batch& scan_batch_ref(dwpa_scan* sc) { return sc->batch; }
+// Whoever takes the batch loads it itself (rules_load): what it holds afterwards is no association load.
+Batch& scan_batch_ref(dwpa_scan* sc) {
+    sc->assoc_loaded = false;
+    return sc->batch;
+}
 int scan_device(const dwpa_scan* sc) { return sc->device; }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2148,6 +2386,23 @@ void dwpa_debug_scan_work(uint64_t out[3], int reset) {
                                  : c[i]->load(std::memory_order_relaxed);
         if (out) out[i] = v;
     }
+}
+
+// And the association runs' work: out[0] = slots derived (one PBKDF2 each), out[1] = segments handed to the verifier.
+// A net whose lines are all retired adds to neither.
+void dwpa_debug_assoc_work(uint64_t out[2], int reset) {
+    std::atomic<uint64_t>* c[2] = {&g_assoc_slots, &g_assoc_segs};
+    for (int i = 0; i < 2; i++) {
+        const uint64_t v = reset ? c[i]->exchange(0u, std::memory_order_relaxed)
+                                 : c[i]->load(std::memory_order_relaxed);
+        if (out) out[i] = v;
+    }
+}
+
+// The records a segment list of a scan starts with from now on (0: the default, a share of the batch); returns the
+// previous setting.  A test sets 1 to see the lists grow.
+uint32_t dwpa_debug_assoc_segcap(uint32_t records) {
+    return g_assoc_segcap.exchange(records, std::memory_order_relaxed);
 }
 
 int dwpa_init(const dwpa_config* cfg) {
@@ -2450,6 +2705,32 @@ int dwpa_scan_load_table(dwpa_scan* scan, uint64_t first, uint32_t count, void* 
     return guarded([&]() -> int {
         if (!scan) RCHK(ensure_init());
         return scan_load_table(scan, first, count, hip_stream);
+    });
+}
+int dwpa_scan_num_nets(const dwpa_scan* scan) { return scan ? (int)scan_num_nets(scan) : DWPA_E_ARG; }
+int64_t dwpa_scan_net_of_line(const dwpa_scan* scan, size_t line) {
+    return scan ? scan_net_of_line(scan, line) : DWPA_E_ARG;
+}
+int dwpa_scan_set_assoc(dwpa_scan* scan, const dwpa_bytes* words, const uint32_t* net_of_word, size_t count,
+                        const char* rules_text, size_t rules_len, uint32_t minlen, uint32_t maxlen,
+                        uint64_t* keyspace) {
+    return guarded([&]() -> int {
+        if (!scan) {  // no scan can exist without a device: say so first
+            RCHK(ensure_init());
+            return DWPA_E_ARG;
+        }
+        if (!rules_text && rules_len) return DWPA_E_ARG;
+        if (rules_len == 0) return scan_set_assoc(scan, words, net_of_word, count, nullptr, minlen, maxlen, keyspace);
+        RuleSet rs;  // rule text takes the whole language, as dwpa_scan_set_rules
+        rs.load_text(rules_text, rules_len);
+        if (rs.size() == 0) return DWPA_E_RULE;
+        return scan_set_assoc(scan, words, net_of_word, count, &rs, minlen, maxlen, keyspace);
+    });
+}
+int dwpa_scan_load_assoc(dwpa_scan* scan, uint64_t first, uint32_t count, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!scan) RCHK(ensure_init());
+        return scan_load_assoc(scan, first, count, hip_stream);
     });
 }
 int dwpa_scan_pbkdf2(dwpa_scan* scan, int group, void* hip_stream) {

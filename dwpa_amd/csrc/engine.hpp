@@ -127,6 +127,17 @@ struct Table;  // table.hpp
 int scan_set_table(dwpa_scan* sc, const uint64_t* d_off, const uint8_t* d_bytes, uint64_t nwords, const Table& t,
                    uint32_t minlen, uint32_t maxlen, uint32_t word_max, uint64_t* keyspace, uint64_t* kept);
 int scan_load_table(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream);
+// the association attack (assoc_dev.hip, assoc.hpp): the scan's nets are the (ESSID, MAC_AP) pairs of its usable lines
+// in order of first appearance.  scan_set_assoc takes the entries of all nets, net-major (net_of_word non-decreasing,
+// every word 1..256 bytes; the scan copies them), builds the index over the nets with W_n x R > 0 and one salt entry per
+// ESSID group; rs == nullptr: the identity.  A refused call leaves the previous association set.  scan_load_assoc
+// generates indices [first, first + count); scan_run then derives each slot with its own net's ESSID and verifies it
+// against that net's live lines only, and scan_pbkdf2 / scan_verify refuse until another kind of load.
+uint32_t scan_num_nets(const dwpa_scan* sc);
+int64_t scan_net_of_line(const dwpa_scan* sc, size_t input_line);  // DWPA_E_ARG: no such line or not usable
+int scan_set_assoc(dwpa_scan* sc, const dwpa_bytes* words, const uint32_t* net_of_word, size_t count, const RuleSet* rs,
+                   uint32_t minlen, uint32_t maxlen, uint64_t* keyspace);
+int scan_load_assoc(dwpa_scan* sc, uint64_t first, uint32_t count, void* stream);
 int scan_pbkdf2(dwpa_scan* sc, int group, void* stream);
 int scan_verify(dwpa_scan* sc, int group, void* stream);
 int scan_run(dwpa_scan* sc, void* stream);

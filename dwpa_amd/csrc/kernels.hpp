@@ -38,6 +38,32 @@ hipError_t launch_table_count(const uint64_t* off, const uint8_t* bytes, uint32_
 hipError_t launch_prep_table(uint64_t first, uint32_t count, uint32_t nkept, const uint64_t* start,
                              const uint32_t* kword, const uint64_t* off, const uint8_t* bytes, const uint8_t* table,
                              uint32_t* mid, uint64_t* ids, uint32_t* counter, uint32_t cap, hipStream_t s);
+// assoc_dev.hip: association candidates [first, first + count) (assoc.hpp) -> midstates in compacted slots, ids[slot] =
+// the raw index, sref[slot] = the word offset of the net's salt entry for launch_pbkdf2_ms, and per verify class c
+// (PMKID, keyver 1, 2, 3) the segments {line, slot, count} of the kept candidates against their own net's live lines:
+// segcnt[c] counts them all, seg[c] holds the first segcap[c].  The counter and segcnt[0..4) are zeroed by the caller;
+// it has checked first + count <= start[nidx] and count <= cap.
+struct AssocEntry {
+    uint32_t wfirst;  // the net's first entry in woff
+    uint32_t nwords;  // W_n >= 1
+    uint32_t net;     // index into net_line_off
+    uint32_t sref;    // word offset of its ESSID's salt entry {nsalt, [2][nsalt][16]}
+};
+struct AssocLaunch {
+    uint32_t nidx = 0;                 // nets that own indices
+    const uint64_t* start = nullptr;   // nidx + 1 prefix sums of W_n x R
+    const AssocEntry* ent = nullptr;   // nidx
+    const uint64_t* woff = nullptr;    // entries + 1 byte offsets into wbytes
+    const uint8_t* wbytes = nullptr;
+    const uint32_t* roffs = nullptr;   // the rule image (RuleSet::flatten); nrules 0: the identity
+    const uint32_t* rcode = nullptr;
+    uint32_t nrules = 0;
+    const uint32_t* net_line_off = nullptr;  // nets + 1 offsets into net_line
+    const uint32_t* net_line = nullptr;      // live lines per net: table line | class index << 30
+};
+hipError_t launch_prep_assoc(const AssocLaunch& a, uint64_t first, uint32_t count, uint32_t minlen, uint32_t maxlen,
+                             uint32_t* mid, uint64_t* ids, uint32_t* sref, uint32_t* counter, uint32_t cap,
+                             SegDev* const seg[4], const uint32_t segcap[4], uint32_t* segcnt, hipStream_t s);
 // hybrid_dev.hip: words [first_word, first_word + nwords) of off/bytes x mask candidates [mask_first, mask_first +
 // mask_count), word-major, joined as word || mask or (mask_then_word) mask || word -> midstates in compacted slots;
 // kept iff len <= 63 and minlen <= len + npos <= min(maxlen, 64); ids[slot] = word * keyspace + mask index.  The

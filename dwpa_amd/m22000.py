@@ -618,6 +618,77 @@ def crack_table(hash_file, dict_file, table_file, word_max: int = 0, skip: int =
                                      _b(out_file), ctypes.byref(cfg))
 
 
+def _opt(path):
+    return None if path is None else _b(path)
+
+
+def _assoc_flags(single) -> int:
+    return L.DWPA_ASSOC_SINGLE if single else 0
+
+
+def assoc_single(hashline, minlen: int = 8) -> list:
+    """The single generator's words for one hashline (host only), in order, duplicates included: from the BSSID b as a
+    48-bit integer the last 12, 10 and 8 hex digits of b - 1, b, b + 1 (mod 2**48) in lower then upper case; from the
+    ESSID e the words e, e1, e123, e! each followed by its ASCII upper and lower case where they differ, those shorter
+    than minlen left out."""
+    ln = _b(hashline)
+    lib = L.load()
+    nw, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    rc = lib.dwpa_assoc_single(ln, len(ln), _u32(minlen, "minlen"), None, 0, None, 0, ctypes.byref(nw), ctypes.byref(nb))
+    if rc != L.DWPA_E_OVERFLOW:
+        L.check(rc, "assoc_single")
+        if rc < 0:
+            raise L.DwpaError(rc, "assoc_single: the hashline does not parse")
+        return []
+    out = ctypes.create_string_buffer(nb.value + 1)
+    lens = (ctypes.c_uint32 * max(1, nw.value))()
+    L.check(lib.dwpa_assoc_single(ln, len(ln), int(minlen), out, nb.value, lens, nw.value, ctypes.byref(nw),
+                                  ctypes.byref(nb)), "assoc_single")
+    raw, words, at = out.raw, [], 0
+    for k in range(nw.value):
+        words.append(raw[at:at + lens[k]])
+        at += lens[k]
+    return words
+
+
+def assoc_plan(hash_file, assoc_file=None, single: bool = False, rules_file=None) -> dict:
+    """The association attack's plan over a hash file (host only; the nets come from the hash file): {keyspace, nets,
+    entries, file_lines, unmatched, malformed, dropped, rules}.  Raises DwpaError for no source, an unreadable file, a
+    rules file that loads no rule, a keyspace above 2**64 - 1 or a net with 2**32 or more word x rule choices."""
+    info = L.AssocInfo()
+    L.check(L.load().dwpa_assoc_plan(_b(hash_file), _opt(assoc_file), _assoc_flags(single), _opt(rules_file),
+                                     ctypes.byref(info)), "assoc_plan")
+    return {n: int(getattr(info, n)) for n, _ in L.AssocInfo._fields_ if n != "reserved"}
+
+
+def assoc_candidates(hash_file, indices, assoc_file=None, single: bool = False, rules_file=None) -> list:
+    """Candidates `indices` of that plan (host only): [(candidate bytes, or None where the index gives none -- the rule
+    rejects, or the result is outside 8..63 bytes --, the first input line of the index's net)]."""
+    idx = [_u64(i, "index") for i in indices]
+    ia = (ctypes.c_uint64 * max(1, len(idx)))(*idx)
+    out = ctypes.create_string_buffer(64 * max(1, len(idx)))
+    ol = (ctypes.c_uint32 * max(1, len(idx)))()
+    fl = (ctypes.c_uint32 * max(1, len(idx)))()
+    L.check(L.load().dwpa_assoc_candidates(_b(hash_file), _opt(assoc_file), _assoc_flags(single), _opt(rules_file), ia,
+                                           len(idx), out, ol, fl), "assoc_candidates")
+    raw = out.raw
+    return [(None if ol[k] == 0xffffffff else raw[64 * k:64 * k + ol[k]], int(fl[k])) for k in range(len(idx))]
+
+
+def crack_assoc(hash_file, assoc_file=None, single: bool = False, rules_file=None, skip: int = 0, limit: int = 0,
+                nonce_error_corrections: int = 8, out_file="help_crack.key", device_mask: int = 0, batch: int = 0,
+                nc_mode: int = L.DWPA_NC_HASHCAT) -> int:
+    """The association attack over hash_file, on every selected device: every net (ESSID, MAC_AP) against its own words
+    -- the MAC_AP:WORD lines of assoc_file, the single generator's with single=True, each under every rule of
+    rules_file -- derived with that net's ESSID and verified against that net's lines only.  skip / limit: indices
+    [skip, skip + limit) of the keyspace (limit 0 = to the end).  Returns a hashcat exit code (0 cracked, 1 exhausted,
+    -1 error)."""
+    cfg = L.Config(ctypes.sizeof(L.Config), device_mask, batch, nc_mode)
+    return L.load().dwpa_crack_assoc(_b(hash_file), _opt(assoc_file), _assoc_flags(single), _opt(rules_file),
+                                     _u64(skip, "skip"), _u64(limit, "limit"), _nc(nonce_error_corrections),
+                                     _b(out_file), ctypes.byref(cfg))
+
+
 def crack_stats():
     """dwpa_crack_last_stats: {words, candidates, hashes, cracked, seconds, rules, rules_skipped, rules_rejmem} of
     this thread's last crack call."""
@@ -792,6 +863,39 @@ class Scan:
         """Table candidates [first, first + count) into slots 0..count-1, generated on the GPU; candidate id = index."""
         L.check(self._lib.dwpa_scan_load_table(self._h, _u64(first, "first"), _u32(count, "count"), stream),
                 "scan_load_table")
+
+    @property
+    def nets(self) -> int:
+        """The scan's nets: the (ESSID, MAC_AP) pairs of its usable lines, numbered by first appearance."""
+        return L.check(self._lib.dwpa_scan_num_nets(self._h), "scan_num_nets")
+
+    def net_of_line(self, i: int) -> int:
+        """The net of input line i (raises DwpaError for a line that is not usable)."""
+        return L.check(self._lib.dwpa_scan_net_of_line(self._h, i), "scan_net_of_line")
+
+    def set_assoc(self, words, net_of_word, rules_text=b"", minlen: int = 8, maxlen: int = 63) -> int:
+        """Set the scan's association: words[i] (1..256 bytes) belongs to net net_of_word[i], net-major (the net
+        numbers never decrease), duplicates already dropped.  rules_text: the whole rule language, empty for none.  Net
+        n then owns W_n x R indices, rule-major with the word fastest.  Returns the keyspace."""
+        ws = list(words)
+        nets = [_u32(n, "net") for n in net_of_word]
+        if len(nets) != len(ws):
+            raise L.DwpaError(L.DWPA_E_ARG, "one net number per word")
+        arr, n, keep = _word_array(ws)
+        na = (ctypes.c_uint32 * max(1, n))(*nets)
+        t = _b(rules_text)
+        k = ctypes.c_uint64(0)
+        L.check(self._lib.dwpa_scan_set_assoc(self._h, arr, na, n, t, len(t), _u32(minlen, "minlen"),
+                                              _u32(maxlen, "maxlen"), ctypes.byref(k)), "scan_set_assoc")
+        self.assoc_keyspace = k.value
+        return k.value
+
+    def load_assoc(self, first: int, count: int, stream: int = 0):
+        """Association indices [first, first + count), generated on the GPU: the kept candidates of nets that still
+        have an uncracked line take compacted slots in index order; candidate id = its index.  run() then derives each
+        slot with its own net's ESSID and verifies it against that net's uncracked lines only."""
+        L.check(self._lib.dwpa_scan_load_assoc(self._h, _u64(first, "first"), _u32(count, "count"), stream),
+                "scan_load_assoc")
 
     def pbkdf2(self, group: int = 0, stream: int = 0):
         L.check(self._lib.dwpa_scan_pbkdf2(self._h, group, stream), "scan_pbkdf2")

@@ -49,7 +49,9 @@ extern "C" {
                                 dwpa_mask_candidate_markov, dwpa_mask_candidates_markov, dwpa_scan_set_mask_markov,
                                 dwpa_crack_mask_markov; the table attack -- dwpa_table_parse, dwpa_table_builtin,
                                 dwpa_table_keyspace, dwpa_table_candidates, dwpa_scan_set_table,
-                                dwpa_scan_load_table, dwpa_crack_table */
+                                dwpa_scan_load_table, dwpa_crack_table; the association attack --
+                                dwpa_assoc_single, dwpa_assoc_plan, dwpa_assoc_candidates, dwpa_scan_num_nets,
+                                dwpa_scan_net_of_line, dwpa_scan_set_assoc, dwpa_scan_load_assoc, dwpa_crack_assoc */
 
 /* ---- return codes ------------------------------------------------------------------------------------------ */
 #define DWPA_MISS 0            /* no key matched (PHP: False)                                                 */
@@ -422,6 +424,70 @@ int dwpa_crack_table(const char *hash_file, const char *dict, const char *table_
                      uint64_t skip, uint64_t limit, int nonce_error_corrections, const char *out_file,
                      const dwpa_config *cfg);
 
+/* ---- association attack: every net against its own words (hashcat -a 9; web/rkg.php's per-net pass) -------------
+ * Every other attack tries one candidate stream against every net of the hash file; this one tries each net's own
+ * words against that net only.
+ * Net.  The pair (ESSID bytes, MAC_AP bytes) of a usable hashline.  Nets are numbered by first appearance in the hash
+ *   file; all usable lines with that pair belong to the net: PMKID and EAPOL of any keyver, any MAC_STA.
+ * Entries.  A net's word list comes from its sources, in order: first the lines of the association file whose key is
+ *   the net's MAC_AP, in file order; then, with DWPA_ASSOC_SINGLE, the built-in generator's words.  Within a net a word
+ *   equal byte for byte to an earlier one is dropped (the first stays); a word of 0 bytes or more than 256 bytes is
+ *   dropped.  W_n words are left; a net with W_n = 0 owns no indices.
+ * Association file.  Read through the dictionary reader: plain or gzip, CRLF accepted.  Each line is MAC_AP:WORD --
+ *   12 hex digits in either case, one ':', then the word; $HEX[...] is decoded for the WORD part only.  A line of
+ *   another shape is skipped with one stderr line and counted (malformed); a line whose MAC matches no net is counted
+ *   (unmatched) and skipped.  A MAC that occurs under two ESSIDs feeds both nets.
+ * Single generator (after web/rkg.php:48-77).  From the BSSID as a 48-bit integer b (a MAC_AP of 6 bytes; another
+ *   length gives no BSSID words): for i in -1, 0, +1 and j in 12, 10, 8 the last j hex digits of (b + i) mod 2^48,
+ *   zero-padded to j, lowercase, then uppercase.  From the ESSID e: for each suffix in "", "1", "123", "!" c = e +
+ *   suffix; c, then its ASCII uppercase if that differs, then its ASCII lowercase if that differs.  ESSID-derived
+ *   words shorter than minlen are omitted: 8 without rules, 1 with rules (so that linksys + $1 is reachable).
+ * Keyspace.  R = the number of loaded rules, 1 (the identity) without a rules file.  Net n owns W_n x R consecutive
+ *   indices from start[n], rule-major with the word fastest: sub = id - start[n], rule = sub / W_n, word = sub % W_n.
+ *   K = start[N]; K above 2^64 - 1 and W_n x R >= 2^32 are refused.  skip / limit name windows of these indices.
+ * Candidate.  The rule applied to the word by the rule engine; a rules file loads as every -r file does.  A rejected
+ *   result, or one outside 8..63 bytes, gives no candidate.
+ * Association.  A candidate of net n is derived with net n's ESSID and verified against the not-yet-cracked lines of
+ *   net n and against nothing else -- not against a line of another net with the same ESSID, though that line would
+ *   accept the same PMK.  A net whose lines are all cracked, or can never match, yields no slots from then on; its
+ *   indices stay in the keyspace.  Two nets that share an ESSID and a word derive that PMK twice, as hashcat -a 9. */
+#define DWPA_ASSOC_SINGLE 1u /* flags: add the single generator's words to every net */
+typedef struct {
+    uint64_t keyspace;   /* K                                                              */
+    uint64_t nets;       /* N                                                              */
+    uint64_t entries;    /* the sum of W_n                                                 */
+    uint64_t file_lines; /* lines of the association file                                  */
+    uint64_t unmatched;  /* of them, well-formed lines whose MAC matches no net            */
+    uint64_t malformed;  /* of them, lines that are not MAC_AP:WORD                        */
+    uint64_t dropped;    /* words dropped: duplicates within a net, 0 bytes, above 256     */
+    uint32_t rules;      /* R                                                              */
+    uint32_t reserved;
+} dwpa_assoc_info;
+/* Host only.  The single generator's words for one hashline (its MAC_AP and ESSID), in order, duplicates included:
+ * word k is lens[k] bytes, the words lie back to back in out.  *nwords and *nbytes (both required) always receive the
+ * totals; DWPA_E_OVERFLOW when out_cap or lens_cap is too small (nothing is written).  A line that does not parse
+ * returns its DWPA_E_* code. */
+int dwpa_assoc_single(const char *line, size_t line_len, uint32_t minlen, uint8_t *out, size_t out_cap,
+                      uint32_t *lens, size_t lens_cap, size_t *nwords, size_t *nbytes);
+/* Host only; reads the hash file (the nets come from it) but needs no device.  assoc_file and rules_file are nullable;
+ * at least one of assoc_file and DWPA_ASSOC_SINGLE is required.  DWPA_E_IO: a file cannot be read; DWPA_E_RULE: no rule
+ * of rules_file loads; DWPA_E_ARG: no source, K above 2^64 - 1, a net with W_n x R >= 2^32. */
+int dwpa_assoc_plan(const char *hash_file, const char *assoc_file, uint32_t flags, const char *rules_file,
+                    dwpa_assoc_info *out);
+/* Host only.  Candidates indices[0..n) of that plan: out = n x 64 bytes (candidate k at out + 64 k, zero beyond its
+ * length), out_len[k] its length or 0xFFFFFFFF where the index gives no candidate (rejected, outside 8..63 bytes),
+ * first_line[k] (nullable) the first input line of its net.  DWPA_E_ARG also for an index >= K. */
+int dwpa_assoc_candidates(const char *hash_file, const char *assoc_file, uint32_t flags, const char *rules_file,
+                          const uint64_t *indices, size_t n, uint8_t *out, uint32_t *out_len, uint32_t *first_line);
+/* The association attack over hash_file, on every selected device: dwpa_crack_table's hash file, outfile records,
+ * return codes (DWPA_RC_*), nonce_error_corrections and cfg handling; skip / limit name the indices [skip, skip +
+ * limit) (limit 0 = to the end).  One stderr line states the nets, entries, unmatched and malformed counts.
+ * DWPA_RC_ERROR before any device is touched, one stderr line each: no source, an unreadable association, rules or
+ * hash file, no rule left, a refused keyspace, skip >= K with K > 0.  K = 0 exhausts. */
+int dwpa_crack_assoc(const char *hash_file, const char *assoc_file /* nullable */, uint32_t flags,
+                     const char *rules_file /* nullable */, uint64_t skip, uint64_t limit,
+                     int nonce_error_corrections, const char *out_file, const dwpa_config *cfg);
+
 /* ---- hybrid attacks: hashcat -a 6 (wordlist || mask) and -a 7 (mask || wordlist) ------------------------------
  * Candidate: mode 6 = word || m, mode 7 = m || word, m a candidate of the mask (the mask language above, 1..63
  * positions, keyspace K).
@@ -711,6 +777,26 @@ int dwpa_scan_set_table(dwpa_scan *scan, const uint64_t *d_offsets, const uint8_
                         const char *table_text, size_t table_len, uint32_t minlen, uint32_t maxlen,
                         uint32_t word_max, uint64_t *keyspace /* nullable */, uint64_t *kept /* nullable */);
 int dwpa_scan_load_table(dwpa_scan *scan, uint64_t first, uint32_t count, void *hip_stream);
+/* The scan's nets ("association attack" above): their number, and the net of an input line (DWPA_E_ARG for a line
+ * that is not usable). */
+int dwpa_scan_num_nets(const dwpa_scan *scan);
+int64_t dwpa_scan_net_of_line(const dwpa_scan *scan, size_t line);
+/* Association candidates.  dwpa_scan_set_assoc takes the entries of all nets, net-major: words[i] (1..256 bytes)
+ * belongs to net net_of_word[i], which never decreases with i; the caller has dropped duplicates.  The scan copies
+ * them, builds the index over the nets that own indices and one salt entry per ESSID, and owns all of it.  rules_text
+ * (rules_len 0: none, R = 1) takes the whole rule language; a candidate is kept when its length is in minlen..
+ * min(maxlen, 63).  *keyspace (nullable) receives K.  DWPA_E_ARG (the previous association stays): a net number out of
+ * range or decreasing, a word of 0 or more than 256 bytes, count >= 2^32, W_n x R >= 2^32, K above 2^64 - 1;
+ * DWPA_E_RULE: no rule parses.
+ * dwpa_scan_load_assoc generates indices [first, first + count): the kept candidates of nets that still have an
+ * uncracked line take compacted slots in index order, the candidate id is its index.  dwpa_scan_run then derives every
+ * slot with its own net's ESSID and verifies it against that net's uncracked lines only; dwpa_scan_pbkdf2 /
+ * dwpa_scan_verify return DWPA_E_ARG until another kind of load.  DWPA_E_ARG: count > batch, first + count > K (also
+ * when the sum wraps), no association set.  Without a device: DWPA_E_NODEV. */
+int dwpa_scan_set_assoc(dwpa_scan *scan, const dwpa_bytes *words, const uint32_t *net_of_word, size_t count,
+                        const char *rules_text, size_t rules_len, uint32_t minlen, uint32_t maxlen,
+                        uint64_t *keyspace /* nullable */);
+int dwpa_scan_load_assoc(dwpa_scan *scan, uint64_t first, uint32_t count, void *hip_stream);
 /* Stages 2 and 3 for ESSID group g (PMKs of the loaded batch, then every uncracked line of that ESSID). */
 int dwpa_scan_pbkdf2(dwpa_scan *scan, int group, void *hip_stream);
 int dwpa_scan_verify(dwpa_scan *scan, int group, void *hip_stream);

@@ -58,6 +58,16 @@ int dwpa_check_m22000(const char *line, size_t line_len, const dwpa_bytes *keys,
 int dwpa_check_batch(const dwpa_job *jobs, size_t njobs, dwpa_result *out, int *rcs);
 int dwpa_device_count(void);
 const char *dwpa_strerror(int code);
+typedef struct { uint64_t keyspace; uint64_t nets; uint64_t entries; uint64_t file_lines; uint64_t unmatched; uint64_t malformed; uint64_t dropped; uint32_t rules; uint32_t reserved; } dwpa_assoc_info;
+typedef struct dwpa_scan dwpa_scan;
+int dwpa_assoc_single(const char *line, size_t line_len, uint32_t minlen, uint8_t *out, size_t out_cap, uint32_t *lens, size_t lens_cap, size_t *nwords, size_t *nbytes);
+int dwpa_assoc_plan(const char *hash_file, const char *assoc_file, uint32_t flags, const char *rules_file, dwpa_assoc_info *out);
+int dwpa_assoc_candidates(const char *hash_file, const char *assoc_file, uint32_t flags, const char *rules_file, const uint64_t *indices, size_t n, uint8_t *out, uint32_t *out_len, uint32_t *first_line);
+int dwpa_crack_assoc(const char *hash_file, const char *assoc_file, uint32_t flags, const char *rules_file, uint64_t skip, uint64_t limit, int nonce_error_corrections, const char *out_file, const dwpa_config *cfg);
+int dwpa_scan_num_nets(const dwpa_scan *scan);
+int64_t dwpa_scan_net_of_line(const dwpa_scan *scan, size_t line);
+int dwpa_scan_set_assoc(dwpa_scan *scan, const dwpa_bytes *words, const uint32_t *net_of_word, size_t count, const char *rules_text, size_t rules_len, uint32_t minlen, uint32_t maxlen, uint64_t *keyspace);
+int dwpa_scan_load_assoc(dwpa_scan *scan, uint64_t first, uint32_t count, void *hip_stream);
 CDEF;
             $lib = getenv('DWPA_LIB') ?: (defined('DWPA_LIB') ? DWPA_LIB : '/opt/dwpa/libdwpa22000.so');
             $ffi = FFI::cdef($cdef, $lib);
