@@ -262,6 +262,8 @@ SIGNATURES = {
     "dwpa_debug_crack_loads": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_int], None),  # test hook, not in the header
     "dwpa_debug_assoc_work": ([ctypes.POINTER(ctypes.c_uint64), ctypes.c_int], None),  # test hook, not in the header
     "dwpa_debug_assoc_segcap": ([ctypes.c_uint32], ctypes.c_uint32),  # test hook, not in the header
+    "dwpa_debug_scan_prepared": ([_P, _P, _P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _P, _P],
+                                 ctypes.c_int),  # test hook, not in the header
 }
 
 # Bit i of dwpa_debug_pbkdf2_kernels' mask (csrc/kernels.hpp Pbkdf2Kernel): the hipcc-scheduled kernels of kernels.hip,
@@ -358,6 +360,24 @@ def assoc_segcap(records: int = 0) -> int:
     """Set the number of records a scan's segment lists start with (test hook; 0: the default); returns the previous
     setting.  A list that is too short is grown and its load repeated."""
     return int(load().dwpa_debug_assoc_segcap(int(records)))
+
+
+def scan_prepared(scan, stream: int = 0, sref: bool = False) -> dict:
+    """The batch of a m22000.Scan as its last load_* prepared it (test hook; no kernel runs): {"count": the kept
+    counter as the kernel left it, not clamped to the batch; "ids": uint64[n]; "mid": uint32[10][n], the HMAC-SHA1 key
+    midstates (ipad h0..h4, opad h0..h4) of slot j in column j; "sref": uint32[n] after an association load when asked
+    for, else None}, n = min(count, the scan's batch)."""
+    import numpy as np
+    cap = int(scan.batch)
+    ids = np.zeros(cap, dtype=np.uint64)
+    mid = np.zeros(10 * cap, dtype=np.uint32)
+    sr = np.zeros(cap, dtype=np.uint32) if sref else None
+    count = ctypes.c_uint32(0)
+    check(load().dwpa_debug_scan_prepared(scan._h, ids.ctypes.data, mid.ctypes.data, cap, ctypes.byref(count),
+                                          sr.ctypes.data if sref else None, stream), "debug_scan_prepared")
+    n = min(count.value, cap)
+    return {"count": count.value, "ids": ids[:n].copy(), "mid": mid[:10 * n].reshape(10, n).copy(),
+            "sref": sr[:n].copy() if sref else None}
 
 
 def check(rc: int, what: str = "") -> int:

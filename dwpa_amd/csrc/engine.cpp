@@ -2763,6 +2763,28 @@ int dwpa_scan_loaded(dwpa_scan* scan, uint32_t* count, void* hip_stream) {
         return 0;
     });
 }
+// Test hook, not declared in include/dwpa22000.h: the batch as the last load prepared it.  *count_out is the kept
+// counter as the kernel left it (not clamped to the batch, unlike dwpa_scan_loaded); n = min(counter, batch, cap)
+// entries are copied: ids_out[n], mid_out[10][n] (the columns 0..n-1 of the SoA midstates, stride n) and, when
+// sref_out is given and the batch holds an association load, sref_out[n].  Launches nothing, changes nothing.
+int dwpa_debug_scan_prepared(dwpa_scan* scan, uint64_t* ids_out, uint32_t* mid_out, uint32_t cap, uint32_t* count_out,
+                             uint32_t* sref_out, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!scan || !ids_out || !mid_out || !count_out) return DWPA_E_ARG;
+        HIPCHK(hipSetDevice(scan->device));
+        HIPCHK(hipStreamSynchronize(as_stream(hip_stream)));
+        HIPCHK(hipMemcpy(count_out, scan->batch.counters.p, 4, hipMemcpyDeviceToHost));
+        const size_t n = std::min(std::min(*count_out, scan->batch_cap), cap);
+        if (!n) return 0;
+        HIPCHK(hipMemcpy(ids_out, scan->batch.ids.p, n * 8, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < 10; k++)
+            HIPCHK(hipMemcpy(mid_out + k * n, (const uint32_t*)scan->batch.mid.p + k * scan->batch_cap, n * 4,
+                             hipMemcpyDeviceToHost));
+        if (sref_out && scan->assoc_loaded && scan->assoc_sref.p)
+            HIPCHK(hipMemcpy(sref_out, scan->assoc_sref.p, n * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 void dwpa_scan_destroy(dwpa_scan* scan) { scan_destroy(scan); }
 
 static int set_dev(int device) {

@@ -27,6 +27,7 @@ from dwpa_amd import m22000 as M  # noqa: E402
 from dwpa_amd.device import Dictionary  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from tests import test_gpu_recall as R  # noqa: E402
+from tests.join_plan import combi_join as join, keeps  # noqa: E402,F401  (the join and the filter)
 from tests.test_gpu_recall import sizes  # noqa: E402,F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,15 +35,6 @@ NC = R.NC
 ONE = (b"combi-recall",)
 RIGHT, LEFT = L.DWPA_COMBI_AMP_RIGHT, L.DWPA_COMBI_AMP_LEFT
 Y_LENGTHS = (0, 1, 2, 3, 4, 5, 7, 8, 9, 30, 31, 32, 33, 55, 56, 62, 63, 64, 300)
-
-
-def join(base, amp, side):
-    return base + amp if side == RIGHT else amp + base
-
-
-def keeps(a, b, minlen=8, maxlen=63):
-    """The filter: both words at most 63 bytes and the joined length inside minlen..maxlen."""
-    return len(a) <= 63 and len(b) <= 63 and minlen <= len(a) + len(b) <= maxlen
 
 
 def load_pairs(base, amp, load):

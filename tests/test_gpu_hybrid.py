@@ -23,6 +23,7 @@ from dwpa_amd import m22000 as M  # noqa: E402
 from dwpa_amd.device import Dictionary  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from tests import test_gpu_recall as R  # noqa: E402
+from tests.join_plan import hybrid_join as join, kept_words  # noqa: E402,F401  (the join and the filter)
 from tests.test_gpu_recall import sizes  # noqa: E402,F401  (the fixture)
 from tests.test_mask import ref_candidate, ref_sets  # noqa: E402
 
@@ -30,14 +31,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NC = R.NC
 ONE = (b"hybrid-recall",)
 H_MASK, H_CUSTOM = b"?1x?2", (b"ab", b"cde")  # K = 6, P = 3
-
-
-def join(word, m, mode):
-    return word + m if mode == 6 else m + word
-
-
-def kept_words(words, npos, minlen=8, maxlen=63):
-    return [i for i, w in enumerate(words) if len(w) <= 63 and minlen <= len(w) + npos <= maxlen]
 
 
 def plant(words, mask, custom, loads, mode, essids, seed):
