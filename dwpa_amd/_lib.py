@@ -264,6 +264,8 @@ SIGNATURES = {
     "dwpa_debug_assoc_segcap": ([ctypes.c_uint32], ctypes.c_uint32),  # test hook, not in the header
     "dwpa_debug_scan_prepared": ([_P, _P, _P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _P, _P],
                                  ctypes.c_int),  # test hook, not in the header
+    "dwpa_debug_scan_pmks": ([_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_uint32, _P],
+                             ctypes.c_int),  # test hook, not in the header
 }
 
 # Bit i of dwpa_debug_pbkdf2_kernels' mask (csrc/kernels.hpp Pbkdf2Kernel): the hipcc-scheduled kernels of kernels.hip,
@@ -378,6 +380,22 @@ def scan_prepared(scan, stream: int = 0, sref: bool = False) -> dict:
     n = min(count.value, cap)
     return {"count": count.value, "ids": ids[:n].copy(), "mid": mid[:10 * n].reshape(10, n).copy(),
             "sref": sr[:n].copy() if sref else None}
+
+
+def scan_pmks(scan, group=None, run: bool = False, stream: int = 0):
+    """The PMKs of a m22000.Scan where its verifier reads them (test hook; no kernel runs): uint32[8][batch], the eight
+    big-endian words of slot j in column j, for the whole batch width -- a slot past the loaded count holds what an
+    earlier derive left there.  run=False: what pbkdf2(g) of any group or the run() of an association load wrote last;
+    run=True: group `group`'s column block of the last run() that was no association run (DwpaError DWPA_E_ARG for a
+    group that launch did not hold)."""
+    import numpy as np
+    if run and group is None:
+        raise DwpaError(DWPA_E_ARG, "run=True reads one group's block: name the group")
+    cap = int(scan.batch)
+    out = np.zeros(8 * cap, dtype=np.uint32)
+    check(load().dwpa_debug_scan_pmks(scan._h, 1 if run else 0, int(group or 0), out.ctypes.data, cap, stream),
+          "debug_scan_pmks")
+    return out.reshape(8, cap)
 
 
 def check(rc: int, what: str = "") -> int:

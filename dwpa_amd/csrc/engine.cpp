@@ -2785,6 +2785,44 @@ int dwpa_debug_scan_prepared(dwpa_scan* scan, uint64_t* ids_out, uint32_t* mid_o
         return 0;
     });
 }
+// Test hook, not declared in include/dwpa22000.h: the PMK words of slots [0, n), n = min(batch, cap), where the
+// verifier reads them: pmk_out[8][n] (word k of slot j at pmk_out[k * n + j]).  Source 0 is batch.pmk (scan_pbkdf2
+// and the association run write it; `group` is ignored), source 1 the column block of ESSID group `group` in mg_pmk as
+// the last scan_run's last launch left it.  A group that launch did not hold -- no scan_run yet, every line of the
+// group cracked, or an earlier launch of a run that needed several, whose columns the later ones overwrote -- gives
+// DWPA_E_ARG.  An association run (scan_run_assoc) writes batch.pmk and touches neither mg_pmk nor mg_chunks: after one,
+// source 1 still gives the block of the last run that was no association run, and source 0 is the one to read.  The
+// whole batch width is copied, not the loaded count: a slot past the count shows what an earlier derive left there.
+// Copies only: launches nothing, changes nothing.
+int dwpa_debug_scan_pmks(dwpa_scan* scan, int source, int group, uint32_t* pmk_out, uint32_t cap, void* hip_stream) {
+    return guarded([&]() -> int {
+        if (!scan || !pmk_out || (source != 0 && source != 1)) return DWPA_E_ARG;
+        const uint32_t bcap = scan->batch_cap;
+        const uint32_t* src = (const uint32_t*)scan->batch.pmk.p;
+        size_t stride = bcap;
+        if (source == 1) {
+            if (group < 0 || group >= (int)scan->groups.size() || scan->mg_chunks.empty() || !scan->mg_pmk.p)
+                return DWPA_E_ARG;
+            const dwpa_scan::Chunk& ch = scan->mg_chunks.back();
+            uint32_t col = ch.ngroups;
+            for (uint32_t k = 0; k < ch.ngroups; k++)  // a group's salt offset names it: every group owns >= 1 block
+                if (scan->mg_gsalt_h[2 * (ch.g0 + k)] == scan->groups[group].salt_off) col = k;
+            if (col == ch.ngroups || (uint64_t)ch.ngroups * bcap > scan->mg_stride ||
+                scan->mg_pmk.n < (size_t)PMK_WORDS * scan->mg_stride * 4)
+                return DWPA_E_ARG;
+            src = (const uint32_t*)scan->mg_pmk.p + (size_t)col * bcap;
+            stride = scan->mg_stride;
+        }
+        if (!src) return DWPA_E_ARG;
+        HIPCHK(hipSetDevice(scan->device));
+        HIPCHK(hipStreamSynchronize(as_stream(hip_stream)));
+        const size_t n = std::min(bcap, cap);
+        if (!n) return 0;
+        for (size_t k = 0; k < PMK_WORDS; k++)
+            HIPCHK(hipMemcpy(pmk_out + k * n, src + k * stride, n * 4, hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
 void dwpa_scan_destroy(dwpa_scan* scan) { scan_destroy(scan); }
 
 static int set_dev(int device) {

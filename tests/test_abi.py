@@ -125,6 +125,24 @@ def test_debug_crack_loads_hook():
     assert r.stdout.strip() == " ".join([zero] * 3)
 
 
+def test_debug_scan_pmks_hook():
+    """dwpa_debug_scan_pmks (the test hook tests/test_gpu_pmk.py reads a scan's PMK buffers with): exported, outside the
+    public header, the PHP cdef and the ABI version, and DWPA_E_ARG for a null scan, a null buffer or an unknown source
+    before anything touches a device."""
+    lib = L.load()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    php = open(os.path.join(root, "php", "dwpa22000.php")).read()
+    hook = "dwpa_debug_scan_pmks"
+    assert hasattr(lib, hook) and hook in L.SIGNATURES
+    assert hook not in declared_symbols() and hook not in open(L.HEADER).read() and hook not in php
+    assert lib.dwpa_abi_version() == 4
+    out = (ctypes.c_uint32 * 32)(*([7] * 32))
+    fake = ctypes.c_void_p(1)  # never dereferenced: the argument checks come first
+    for scan, source, buf in ((None, 0, out), (None, 1, out), (fake, 0, None), (fake, 2, out), (fake, -1, out)):
+        assert lib.dwpa_debug_scan_pmks(scan, source, 0, buf, 4, None) == L.DWPA_E_ARG
+    assert list(out) == [7] * 32
+
+
 def test_hc_unhex_matches_oracle():
     import dwpa_amd
     for k in [b"$HEX[414243]", b"$HEX[]", b"$HEX[41424]", b"$HEX[41zz]", b"$HEX[4142]x", b"plain", b"$HEX[00ff]",
